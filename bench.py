@@ -9,7 +9,14 @@ RCCL all_reduce of [grads | EMA sums | reset rows | losses] per step. `--gpus N`
 `python bench.py --gpus N` starts the N ranks itself (a child `torch.distributed.run`, 127.0.0.1 rendezvous);
 under a launcher each rank refuses to run unless WORLD_SIZE == N.
 
-Prints ONE JSON line on rank 0. Also reports:
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times `--steps` steps, writes its outputs when
+`--dump-outputs DIR` is given and prints the line (`value`, `ms_per_step`, ...). `--dump-outputs DIR` writes what the
+last timed train_step left its caller as DIR/<name>.npy (rank 0): `metrics` (the returned running-mean dict, float64,
+in VQVAE.metric_names order), `weights` and `grads` (the flat fp32 parameter store after the step and the gradient it
+applied) and `codebook_<l>` (level l's embeddings after its EMA); the batches and the initial weights are seeded, so
+two builds given the same arguments can be compared array for array. `--full` adds the legs below (each still has its
+own --no-* switch), as extra keys of the same line:
+  config2_fp32, config4_prior_train, config5_upsampler_decode — the fp32 leg and the prior legs (fp32_leg, prior_legs);
   roofline     — the dominant kernel (fused residual-block backward) — its algorithmic bytes (SURVEY §8d layer
                  model) / its average duration: its launches of one step are recorded after the timed region
                  and timed back to back in hipGraphs with HIP events on the stream it runs on; `traffic` =
@@ -51,6 +58,10 @@ def parse():
     p.add_argument("--seq", type=int, default=65536)
     p.add_argument("--dtype", default="bf16")
     p.add_argument("--no-graph", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (metrics, weights, grads, codebooks) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the roofline replays, the fp32 / prior legs and the CPU baseline (extra keys)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-roofline", action="store_true", help="skip the roofline replays (PMC passes)")
     p.add_argument("--cpu-batch", type=int, default=8)
@@ -352,8 +363,9 @@ def main():
     if dist.is_initialized():
         dist.barrier()
     t0 = time.perf_counter()
+    res = None
     for i in range(a.steps):
-        model.train_step(batches[i % 4])
+        res = model.train_step(batches[i % 4])
     torch.cuda.synchronize()
     if dist.is_initialized():
         dist.barrier()
@@ -363,8 +375,72 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     loss = float(model.results()["loss"])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, res)  # before any --full leg runs the model again
 
-    # roofline: record the dominant kernel's launches of one step, then time them back to back
+    legs = {}
+    if a.full:
+        legs["roofline"] = roofline_leg(a, V, model, batches)
+        if not a.no_fp32 and a.dtype == "bf16":
+            try:
+                legs["config2_fp32"] = fp32_leg(a, dev, world, batches)
+            except Exception as e:  # an extra leg must never cost the config-2 line
+                legs["config2_fp32"] = {"error": f"{type(e).__name__}: {e}"[:400]}
+        if not a.no_prior:
+            try:
+                legs.update(prior_legs(a, dev, world, rank))
+            except Exception as e:  # an extra leg must never cost the config-2 line
+                legs["prior_legs_error"] = f"{type(e).__name__}: {e}"[:400]
+
+    out = None
+    if rank == 0:
+        if a.full:
+            legs["cpu_baseline"] = cpu_baseline(a.cpu_batch, a.cpu_steps, a.seq) if (
+                world == 1 and not a.no_cpu_baseline) else None
+        # value: the whole job's audio-samples/s (all ranks; the driver derives scaling from it);
+        # value_per_gpu: the metric's per-GPU reading (B_per_gpu * T * steps / wall-seconds)
+        value = a.batch * a.seq * a.steps * world / elapsed
+        out = {"metric": METRIC, "value": round(value, 1), "value_per_gpu": round(value / world, 1),
+               "value_is": "whole-job aggregate over n_gpus (the bench contract: total audio-samples/s of all ranks); "
+                           "value_per_gpu is the metric's per-GPU reading",
+               "unit": "audio-samples/s", "n_gpus": world,
+               "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 3),
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
+               "data": "synthetic 44.1 kHz sine+noise chunks (SURVEY.md §8d) generated on the device "
+                       "(vqa_synthetic_batch), random-init weights",
+               "config": {"workload": "SMALL_VQ_VAE 3-level VQ-VAE train step (BASELINE config 2)",
+                          "model": "VQVAE levels=3 latent=64 K=2048 down_depth=[3,2,2] width=32 depth=4 dil=3",
+                          "global_batch": a.batch * world, "seq_len": a.seq, "parallelism": f"dp{world}",
+                          "graph": not a.no_graph, "final_loss": round(loss, 5),
+                          "exchange": ("per-level, overlapped" if model.overlap_exchange else "one bucket after the join")
+                          if dist.is_initialized() else None},
+               "full": a.full, **legs}
+        if dist.is_initialized() and model.overlap_exchange:
+            out["config"]["exchange_note"] = ("VQA_DP_OVERLAP=1 forced the per-level exchange on; its captured "
+                                              "multi-rank form had not run on hardware before this line (DESIGN.md §5)")
+        print(json.dumps(out), flush=True)
+    if dist.is_initialized():
+        dist.barrier()
+        import vqa_dp
+        vqa_dp.reset()
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, model, res):
+    """--dump-outputs: what the last timed train_step left its caller, as out_dir/<name>.npy (a few MB in all)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"metrics": np.array([float(res[n]) for n in model.metric_names], np.float64),
+              "weights": model.store.flat.detach().cpu().numpy(),
+              "grads": model.store.grad[:model.store.size].detach().cpu().numpy()}
+    for l, st in enumerate(model.get_vq_state()):
+        arrays[f"codebook_{l}"] = st["embeddings"]
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+def roofline_leg(a, V, model, batches):
+    """--full: record the dominant kernel's launches of one step, then time them back to back."""
     with KernelTimer(V) as kt:
         model._compute(batches[0], True)
     torch.cuda.synchronize()
@@ -408,51 +484,7 @@ def main():
         roof["mfma"] = {"tflops": round(fl / (us_total * 1e-6) / 1e12, 1), "peak_tflops": BF16_DENSE_TFLOPS,
                         "frac": round(fl / (us_total * 1e-6) / 1e12 / BF16_DENSE_TFLOPS, 4),
                         "busy_frac_pmc": pmc.get("mfma_busy_frac")}
-
-    legs = {}
-    if not a.no_fp32 and a.dtype == "bf16":
-        try:
-            legs["config2_fp32"] = fp32_leg(a, dev, world, batches)
-        except Exception as e:  # an extra leg must never cost the config-2 line
-            legs["config2_fp32"] = {"error": f"{type(e).__name__}: {e}"[:400]}
-    if not a.no_prior:
-        try:
-            legs.update(prior_legs(a, dev, world, rank))
-        except Exception as e:  # an extra leg must never cost the config-2 line
-            legs["prior_legs_error"] = f"{type(e).__name__}: {e}"[:400]
-
-    out = None
-    if rank == 0:
-        cpu = None
-        if world == 1 and not a.no_cpu_baseline:
-            cpu = cpu_baseline(a.cpu_batch, a.cpu_steps, a.seq)
-        # value: the whole job's audio-samples/s (all ranks; the driver derives scaling from it);
-        # value_per_gpu: the metric's per-GPU reading (B_per_gpu * T * steps / wall-seconds)
-        value = a.batch * a.seq * a.steps * world / elapsed
-        out = {"metric": METRIC, "value": round(value, 1), "value_per_gpu": round(value / world, 1),
-               "value_is": "whole-job aggregate over n_gpus (the bench contract: total audio-samples/s of all ranks); "
-                           "value_per_gpu is the metric's per-GPU reading",
-               "unit": "audio-samples/s", "n_gpus": world,
-               "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 3),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype,
-               "data": "synthetic 44.1 kHz sine+noise chunks (SURVEY.md §8d) generated on the device "
-                       "(vqa_synthetic_batch), random-init weights",
-               "config": {"workload": "SMALL_VQ_VAE 3-level VQ-VAE train step (BASELINE config 2)",
-                          "model": "VQVAE levels=3 latent=64 K=2048 down_depth=[3,2,2] width=32 depth=4 dil=3",
-                          "global_batch": a.batch * world, "seq_len": a.seq, "parallelism": f"dp{world}",
-                          "graph": not a.no_graph, "final_loss": round(loss, 5),
-                          "exchange": ("per-level, overlapped" if model.overlap_exchange else "one bucket after the join")
-                          if dist.is_initialized() else None},
-               "roofline": roof, "cpu_baseline": cpu, **legs}
-        if dist.is_initialized() and model.overlap_exchange:
-            out["config"]["exchange_note"] = ("VQA_DP_OVERLAP=1 forced the per-level exchange on; its captured "
-                                              "multi-rank form had not run on hardware before this line (DESIGN.md §5)")
-        print(json.dumps(out), flush=True)
-    if dist.is_initialized():
-        dist.barrier()
-        import vqa_dp
-        vqa_dp.reset()
-        dist.destroy_process_group()
+    return roof
 
 
 if __name__ == "__main__":

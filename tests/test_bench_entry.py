@@ -5,11 +5,14 @@
 - A bare `bench.py --gpus N` (N > 1, no WORLD_SIZE) is the launcher: it starts torch.distributed.run as a child.
   Here (no GPU) the RCCL form stops before that with a clear error naming the visible-GPU count; the GPU test
   `tests/test_gpu_dp.py::test_bench_py_bare_gpus2_spawns_ranks` runs the spawned ranks.
+- One GPU test: a plain run carries none of the `--full` legs and `--dump-outputs` writes the last step's arrays.
 """
+import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,6 +45,38 @@ def test_gpus_must_be_positive():
     p = subprocess.run([sys.executable, BENCH, "--gpus", "0"], env=_env(), capture_output=True, text=True,
                        timeout=300, cwd=ROOT)
     assert p.returncode == 2 and "--gpus must be >= 1" in p.stderr
+
+
+def _plain_run(out_dir, *extra):
+    cmd = [sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--seq", "8192",
+           "--dump-outputs", str(out_dir), *extra]
+    p = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-4000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(out_dir, f)) for f in sorted(os.listdir(out_dir))}
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_its_outputs(cuda, tmp_path):
+    """A plain run prints the headline line with none of the --full legs, and --dump-outputs writes what the last
+    timed train_step left its caller: the returned metrics, the weights, the gradient, the codebooks (fp32 / fp64,
+    far below 64 MB). The batches and the initial weights are seeded: a second run gives the same arrays."""
+    out, got = _plain_run(tmp_path / "a")
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["dtype"] == "bf16" and out["higher_is_better"] is True
+    want = 2 * 8192 / (out["ms_per_step"] * 1e-3)
+    assert abs(out["value"] - want) <= 1e-3 * want
+    for k in ("roofline", "cpu_baseline", "config2_fp32", "config4_prior_train", "config5_upsampler_decode"):
+        assert k not in out, k
+    assert sorted(got) == ["codebook_0", "codebook_1", "codebook_2", "grads", "metrics", "weights"]
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in got.values())
+    assert sum(v.nbytes for v in got.values()) < 64 << 20
+    assert got["metrics"].shape == (4 + 7 * 3,) and round(float(got["metrics"][0]), 5) == out["config"]["final_loss"]
+    assert got["weights"].shape == got["grads"].shape and np.abs(got["grads"]).max() > 0
+    assert all(got[f"codebook_{l}"].shape == (64, 2048) for l in range(3))
+    _, again = _plain_run(tmp_path / "b")
+    for k in got:
+        assert np.array_equal(got[k], again[k]), f"{k} differs between two runs with the same arguments"
 
 
 def test_launcher_command_shape(monkeypatch):

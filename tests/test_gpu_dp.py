@@ -411,8 +411,8 @@ def test_bench_py_dp2_gloo_one_gpu(cuda):
     env = dict(os.environ, VQA_DIST_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "2", "--seq", "8192", "--no-cpu-baseline",
-           "--prior-batch", "1", "--prior-steps", "2"]
+           "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "2", "--seq", "8192", "--full",
+           "--no-cpu-baseline", "--prior-batch", "1", "--prior-steps", "2"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=540, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

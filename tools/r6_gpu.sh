@@ -174,7 +174,7 @@ suite)
     || { tail -60 $OUT/suite.log; exit 1; }
   tail -3 $OUT/suite.log
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 || exit 1
-  timeout -k 10 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+  timeout -k 10 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/bench.json')); print(d['ms_per_step'], d['value'], d['roofline']['avg_launch_us'], {k: (v.get('ms_per_step'), v.get('value')) for k, v in d.items() if k.startswith('config')})" ;;
 close)
   [ -n "$VQA_COMMIT" ] || { echo "close: set VQA_COMMIT (the git HEAD sent)"; exit 2; }

@@ -17,9 +17,9 @@ cp profiles/pmc_traffic.json "$OUT/pmc_traffic.json"
 # per-kernel durations are taken with the levels serialised (VQA_LEVEL_STREAMS=0): with the levels on
 # concurrent streams a kernel's duration includes the share of the GPU its neighbours take
 VQA_LEVEL_STREAMS=0 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o t -- \
-  python bench.py --no-fp32 > "$OUT/bench_serial.json" 2> "$OUT/bench_serial.err" || { echo "serial bench failed"; exit 1; }
+  python bench.py --full --no-fp32 > "$OUT/bench_serial.json" 2> "$OUT/bench_serial.err" || { echo "serial bench failed"; exit 1; }
 # the bench line itself: default settings, no profiler
-timeout -k 10 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; exit 1; }
+timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; exit 1; }
 find "$OUT/pmc_fetch" "$OUT/pmc_write" "$OUT/pmc_mfma" -name "*counter_collection.csv" -size +20M -delete
 find "$OUT/trace" -name "*kernel_trace.csv" -size +20M -delete
 python tools/stats_summary.py "$OUT/trace/t_kernel_stats.csv" "$OUT/bench_serial.json" "$OUT/bench.json" > "$OUT/summary.md"
