@@ -396,7 +396,12 @@ int vqa_rowsum(const float* x, int64_t rows, int64_t n, float scale, float* out,
  * input tokens (teacher-forced check), logits (N, steps, bins) output. width 128, attention width 32.
  * out_kernel is (width, out_ld) row-major with out_ld >= bins a multiple of 4 and out_bias has out_ld entries
  * (a vocabulary that is not a multiple of 4, e.g. the sampler's default 513 bins, is passed zero-padded; the
- * padded columns are never sampled). */
+ * padded columns are never sampled).
+ * Accepted shapes (VQA_E_UNSUPPORTED otherwise): depth <= 8, heads 1, 2 or 4, and with l = ctx / blocks
+ * l <= 2048 and heads * max(l, blocks) <= VQA_DECODE_SCORE_FLOATS: the kernel's softmax scratch is one LDS array
+ * of that many floats, `heads` rows of max(l, blocks) (a row or previous-row layer scores up to l keys per head,
+ * a column layer up to `blocks`). 1 or 2 heads reach blocks of 2048 tokens, 4 heads blocks of 1024. */
+#define VQA_DECODE_SCORE_FLOATS 4096
 typedef struct {
   const float *ln1_gamma, *ln1_beta, *qkv_kernel, *qkv_bias, *query_kernel, *query_bias, *key_kernel, *key_bias,
       *value_kernel, *value_bias, *out_kernel, *out_bias, *proj_kernel, *proj_bias, *ln2_gamma, *ln2_beta,

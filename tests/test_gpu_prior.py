@@ -713,3 +713,84 @@ def test_random_sample_search_matches_oracle_scores(cuda):
                 cands.append((float(got[k]), out[k]))
     want = min(cands, key=lambda c: c[0])
     assert abs(best_loss - want[0]) < 1e-6 and torch.equal(best.cpu(), want[1])
+
+
+# ------------------------------------------------------------------ other block lengths, block counts and heads
+def _cfg3(ctx, blocks, heads):
+    cfg = P.PriorConfig(bins=64, ctx=ctx, width=128, depth=3, heads=heads, blocks=blocks, attn_stacks=1)
+    assert sorted(cfg.attn_func(i) for i in range(cfg.depth)) == [0, 1, 2]  # row, column and previous row
+    return cfg
+
+
+@pytest.mark.parametrize("ctx,blocks", [(128, 2), (512, 8), (192, 1), (384, 2)])
+def test_model_logits_match_oracle_shapes(cuda, ctx, blocks):
+    """Logits at 2, 8 and 1 blocks of one key tile and at blocks of three tiles (l = 192)."""
+    cfg = _cfg3(ctx, blocks, 2)
+    m, p = _model(cfg, seed=5)
+    tok = torch.randint(0, cfg.bins, (2, cfg.ctx), generator=_gen(ctx + blocks))
+    logits, _ = m(tok)
+    torch.cuda.synchronize()
+    assert _rel(logits, P.model_forward(p, cfg, tok)) < 2e-5
+
+
+def test_train_step_multi_tile_blocks_matches_oracle(cuda):
+    """One fp32 train step at ctx 384 in 2 blocks (l = 192: three key tiles per block): the glue around the
+    attention kernels, the value-bias gradient from block 0 of the previous-row layer included."""
+    cfg = _cfg3(384, 2, 2)
+    pr, vals = _prior(cfg, seed=19)
+    g = _gen(37)
+    codes = torch.randint(0, cfg.bins - 1, (2, cfg.ctx), generator=g)
+    mask = torch.rand(2, cfg.ctx, generator=g) < 0.2
+    loss, acc, grads, bi = P.train_step_grads(P.to_torch(vals), cfg, codes, mask)
+    res = pr.train_step(codes.cuda(), tf_mask=mask.cuda())
+    torch.cuda.synchronize()
+    assert torch.equal(pr._last_batch_input.cpu(), bi)
+    assert abs(float(res["loss"]) - loss) <= 1e-5 * abs(loss)
+    worst, err = _grad_errs(pr.prior.store.grads(), grads)
+    assert err < 2e-4, (worst, err)
+    vb = "prior/layer2/mha/value/bias"
+    assert float(grads[vb].abs().max()) > 0  # the previous-row layer's value bias does receive a gradient
+
+
+# (ctx, blocks, heads, L, N). l = 12: the decode has no multiple-of-64 rule, L = ctx runs the last position; one
+# block: previous row is always the value bias, a column is one key; head dim 32 with more than 256 row keys (the
+# idx += 256 loop wraps); 4 heads (head dim 8); and the two ends of the score scratch's rule heads * max(l, blocks)
+# <= 4096: 4 heads of 1024-token blocks, 2 heads over 2048 one-token blocks (columns of up to 2048 keys)
+DECODE_SHAPES = [(96, 8, 2, 96, 2), (192, 1, 2, 192, 2), (640, 2, 1, 640, 2), (96, 8, 4, 96, 2),
+                 (1024, 1, 4, 1024, 2), (2048, 2048, 2, 2048, 1)]
+
+
+@pytest.mark.parametrize("ctx,blocks,heads,L,N", DECODE_SHAPES)
+def test_decode_teacher_forced_logits_shapes(cuda, ctx, blocks, heads, L, N):
+    cfg = _cfg3(ctx, blocks, heads)
+    m, p = _model(cfg, seed=23)
+    tok = torch.randint(0, cfg.bins, (N, L + 1), generator=_gen(ctx + heads))
+    tok[:, 0] = cfg.bins - 1
+    _, logits = m.sample(N, max_length=L, forced=tok.cuda(), return_logits=True, seed=5)
+    torch.cuda.synchronize()
+    ref = P.model_forward(p, cfg, tok[:, :L])
+    assert _rel(logits, ref) < 2e-5
+
+
+@pytest.mark.parametrize("ctx,blocks,heads,msg", [
+    (1025, 1, 4, r"heads 4 x max\(block length 1025, blocks 1\) exceeds the 4096-float score scratch"),
+    (2049, 2049, 2, r"heads 2 x max\(block length 1, blocks 2049\) exceeds the 4096-float score scratch"),
+    (4097, 4097, 1, r"heads 1 x max\(block length 1, blocks 4097\) exceeds the 4096-float score scratch"),
+    (2049, 1, 1, r"heads 1 block 2049 unsupported"),
+    (64, 1, 8, r"heads 8 block 64 unsupported")])
+def test_decode_rejects_shapes_past_the_score_scratch(cuda, ctx, blocks, heads, msg):
+    """Just past what the decode kernel's score scratch holds (include/vqa.h): sample() raises ValueError and the
+    entry point itself returns VQA_E_UNSUPPORTED (-2); nothing is launched."""
+    import vqa_lib as V
+    cfg = P.PriorConfig(bins=64, ctx=ctx, width=128, depth=3, heads=heads, blocks=blocks, attn_stacks=1)
+    m, _ = _model(cfg)
+    assert V.decode_shape_error(ctx, heads, blocks) is not None
+    with pytest.raises(ValueError, match="decode"):
+        m.sample(1, max_length=1)
+    layers = [ly.layer_desc() for ly in m.transformer.layers]
+    tokens = torch.zeros(1, 2, dtype=torch.int64, device="cuda")
+    with pytest.raises(V.VQAError, match=r"\(-2\): prior_decode: .*" + msg):
+        V.prior_decode(layers, m.store.view(m.emb_name), m._pos().contiguous(), m.store.view(m.out_kernel),
+                       m.store.view(m.out_bias), tokens, m.decode_cache(1), 1, ctx, heads, blocks, m.start_token, 0)
+    for c, b, h, *_ in DECODE_SHAPES:
+        assert V.decode_shape_error(c, h, b) is None

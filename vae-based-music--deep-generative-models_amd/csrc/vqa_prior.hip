@@ -1528,6 +1528,13 @@ constexpr int kDecMaxLayers = 8;
 constexpr int kDecW = 128;   // model width
 constexpr int kDecAW = 32;   // attention width (m_attn 0.25)
 constexpr int kDecMaxL = 2048;
+// Softmax scratch of the decode kernel: heads rows of `scs` floats in one flat LDS array. A layer scores at most
+// max(l, blocks) keys per head (row: p + 1 <= l; column: b + 1 <= blocks; previous row: l), so scs = max(l, blocks)
+// and vqa_prior_decode accepts only heads * scs <= kDecScoreFloats: every sc[h * scs + idx] with h < heads and
+// idx < cnt <= scs is then below heads * scs <= kDecScoreFloats. (2 heads of 2048-token blocks fill it; the
+// kernel's other static LDS leaves no room for more.)
+constexpr int kDecScoreFloats = VQA_DECODE_SCORE_FLOATS;
+static_assert(kDecScoreFloats == 2 * kDecMaxL, "decode score scratch: 2 heads of kDecMaxL keys");
 
 struct DecLayer {
   const float *ln1g, *ln1b, *qkvw, *qkvb, *qw, *qb, *kw, *kb, *vw, *vb, *ow, *ob, *pw, *pb, *ln2g, *ln2b, *mw, *mb;
@@ -1548,6 +1555,7 @@ struct DecArgs {
   float* kc;              // (N, depth, T, 32) key cache
   float* vc;              // (N, depth, T, 32) value cache
   int N, steps, T, depth, H, l, bins, ldo;  // ldo: head weight row stride (>= bins, % 4 == 0)
+  int scs;                // row stride of the score scratch: max(l, T / l); H * scs <= kDecScoreFloats
   long long start;
   unsigned long long seed;
   float scale, emb_scale, eps;
@@ -1641,7 +1649,7 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
   __shared__ __attribute__((aligned(16))) float x[kDecW], x1[kDecW], hb[kDecW], r1[kDecW];
   __shared__ float ring[kDecMaxLayers][3][kDecW];
   __shared__ __attribute__((aligned(16))) float cat[3 * kDecW], qkv[3 * kDecAW], oh[kDecAW];
-  __shared__ float sc[2][kDecMaxL];
+  __shared__ float sc[kDecScoreFloats];  // [H][a.scs], see kDecScoreFloats
   __shared__ __attribute__((aligned(16))) float scr[2048];
   __shared__ __attribute__((aligned(16))) float red[32][kDecAW];
   __shared__ float stat[4];
@@ -1711,7 +1719,7 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
               const f32x4 pq = qv[c] * kv[c];
               s += (pq[0] + pq[1]) + (pq[2] + pq[3]);
             }
-            sc[h][idx] = s * a.scale;
+            sc[h * a.scs + idx] = s * a.scale;
           }
         }
         __syncthreads();
@@ -1719,12 +1727,13 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
         if (wave < a.H) {
           float m = -INFINITY;
-          for (int idx = lane; idx < cnt; idx += 64) m = fmaxf(m, sc[wave][idx]);
+          float* scw = sc + wave * a.scs;
+          for (int idx = lane; idx < cnt; idx += 64) m = fmaxf(m, scw[idx]);
           m = wave_max_f(m);
           float su = 0.f;
           for (int idx = lane; idx < cnt; idx += 64) {
-            const float e = __expf(sc[wave][idx] - m);
-            sc[wave][idx] = e;
+            const float e = __expf(scw[idx] - m);
+            scw[idx] = e;
             su += e;
           }
           su = wave_sum_f(su);
@@ -1735,10 +1744,11 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
         // sl, sl + 32, ... with 16-byte loads; slices combined in a fixed order
         {
           const int c4 = tid & 7, sl = tid >> 3, h = 4 * c4 / hd;
+          const float* sch = sc + h * a.scs;
           f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
           for (int idx = sl; idx < cnt; idx += 32)
-            acc = acc + sc[h][idx] * *(const f32x4*)(vcL + (size_t)(j0 + idx * jstep) * kDecAW + 4 * c4);
+            acc = acc + sch[idx] * *(const f32x4*)(vcL + (size_t)(j0 + idx * jstep) * kDecAW + 4 * c4);
           *(f32x4*)(&red[sl][4 * c4]) = acc;
         }
         __syncthreads();
@@ -2234,6 +2244,11 @@ extern "C" int vqa_prior_decode(const vqa_prior_layer* layers, int depth, const 
                   kDecAW / heads <= 32 && ctx / blocks <= kDecMaxL && heads <= 4,
               VQA_E_UNSUPPORTED, "prior_decode: depth %d width %d heads %d block %d unsupported", depth, width, heads,
               ctx / blocks);
+  // the score scratch holds `heads` rows of max(block length, blocks) floats (kDecScoreFloats, above)
+  const int scs = ctx / blocks > blocks ? ctx / blocks : blocks;
+  VQA_REQUIRE((long long)heads * scs <= kDecScoreFloats, VQA_E_UNSUPPORTED,
+              "prior_decode: heads %d x max(block length %d, blocks %d) exceeds the %d-float score scratch", heads,
+              ctx / blocks, blocks, kDecScoreFloats);
   VQA_ARG(cache_bytes >= vqa_prior_decode_cache_bytes(N, depth, ctx), "prior_decode: cache too small");
   DecArgs a;
   float* comp = (float*)cache + (size_t)2 * N * depth * ctx * kDecAW;
@@ -2252,6 +2267,7 @@ extern "C" int vqa_prior_decode(const vqa_prior_layer* layers, int depth, const 
   a.kc = (float*)cache;
   a.vc = (float*)cache + (size_t)N * depth * ctx * kDecAW;
   a.N = N; a.steps = steps; a.T = ctx; a.depth = depth; a.H = heads; a.l = ctx / blocks; a.bins = bins; a.ldo = out_ld;
+  a.scs = scs;
   a.start = start; a.seed = seed;
   a.scale = 1.0f / sqrtf((float)(kDecAW / heads));
   a.emb_scale = sqrtf((float)width);

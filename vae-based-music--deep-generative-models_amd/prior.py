@@ -429,6 +429,9 @@ class FMHABasedAutoregressiveModel:
         L = self.context_length if max_length is None else int(max_length)
         if not 0 < L <= self.context_length:
             raise ValueError(f"max_length {L} outside (0, {self.context_length}]")
+        why = V.decode_shape_error(self.context_length, self.heads, self.blocks)
+        if why is not None:
+            raise ValueError(f"sample(): {why}")
         xc = None
         if x_cond is not None:
             # autoregressive_fmha.py:145-148 asserts x_cond is [n_samples, max_length, d_model] before adding it:

@@ -732,6 +732,25 @@ class PriorLayerDesc(ctypes.Structure):
         "mlp_kernel", "mlp_bias")] + [("attn_type", ctypes.c_int)]
 
 
+# vqa_prior_decode's softmax scratch (VQA_DECODE_SCORE_FLOATS, include/vqa.h): `heads` rows of max(block length,
+# blocks) floats must fit it, and a block is at most DECODE_MAX_BLOCK_LEN tokens
+DECODE_SCORE_FLOATS = 4096
+DECODE_MAX_BLOCK_LEN = 2048
+
+
+def decode_shape_error(ctx, heads, blocks) -> Optional[str]:
+    """None if vqa_prior_decode accepts (ctx, heads, blocks), else the rule it breaks (include/vqa.h)."""
+    l = ctx // blocks
+    if heads not in (1, 2, 4):
+        return f"decode supports 1, 2 or 4 heads (got {heads})"
+    if l > DECODE_MAX_BLOCK_LEN:
+        return f"decode supports blocks of at most {DECODE_MAX_BLOCK_LEN} tokens (got {l})"
+    if heads * max(l, blocks) > DECODE_SCORE_FLOATS:
+        return (f"decode needs heads * max(block length, blocks) <= {DECODE_SCORE_FLOATS} "
+                f"(got {heads} * max({l}, {blocks}))")
+    return None
+
+
 def prior_decode(layers, emb, pos, out_w, out_b, tokens, cache, steps, ctx, heads, blocks, start, seed, ycond=None,
                  xcond=None, forced=None, logits=None, bins=None):
     """out_w (width, ld) / out_b (ld,) with ld a multiple of 4 >= bins (zero-padded columns are never sampled)."""
