@@ -61,3 +61,20 @@ class VQVAESampler:
     def sample_level(self, zs, level):
         """Sampler.py:116-124 (a stub in the reference)."""
         return NotImplementedError
+
+
+def window_starts(total_length, n_ctx, hop_length) -> List[int]:
+    """Starts of the windows of n_ctx codes that cover total_length codes of one level (the window rule of
+    long-form sampling): 0, hop, 2 hop, ... while the window ends before total_length, then a last window that
+    ends exactly there (total_length - n_ctx; every earlier start is below it, so no start repeats). Each window
+    after the first shares n_ctx - hop codes (more for the last) with the windows before it."""
+    if total_length < n_ctx:
+        raise ValueError(f"total_length {total_length} is shorter than one window of {n_ctx}")
+    if not 1 <= hop_length <= n_ctx:
+        raise ValueError(f"hop_length {hop_length} outside [1, {n_ctx}]")
+    starts, start = [], 0
+    while start + n_ctx < total_length:
+        starts.append(start)
+        start += hop_length
+    starts.append(total_length - n_ctx)
+    return starts
