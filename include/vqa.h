@@ -414,6 +414,26 @@ int vqa_prior_decode(const vqa_prior_layer* layers, int depth, const float* x_em
                      const int64_t* forced, float* logits, int64_t* tokens, void* cache, size_t cache_bytes, int N,
                      int steps, int ctx, int width, int heads, int blocks, int bins, int out_ld, int64_t start,
                      uint64_t seed, vqa_stream_t stream);
+/* vqa_prior_decode with a prime, a temperature and top-k (vqa_prior_decode forwards here with NULL, 0, 1.0f, 0;
+ * those defaults run the unfiltered kernel and give its bits).
+ * prime (N, prime_len) int64, 0 <= prime_len <= steps: tokens[n][j] = prime[n][j-1] for 1 <= j <= prime_len and
+ * the later entries are sampled. A primed step does everything up to the output head (key/value cache, LayerNorm
+ * ring) and takes the prime's token as the next input; its head, noise and argmax run only when `logits` is
+ * given. The noise stays keyed by (seed, sample, absolute step, bin): a decode primed with the first P tokens of
+ * an unprimed decode of the same seed reproduces the rest bit for bit. A window of long-form sampling is primed
+ * with the codes it shares with the windows before it.
+ * temperature (finite, > 0): score = logit / temperature + G. top_k in [0, bins], 0 and bins meaning off: only
+ * the bins whose logit is >= the k-th largest logit of the row take part in the argmax (every bin tied with the
+ * k-th value stays in; ties of the score go to the lowest index). The k-th value is found by a radix select of
+ * four fixed rounds, whatever the data.
+ * VQA_E_INVALID_ARG before any launch: prime_len outside [0, steps], prime_len > 0 without a prime, a prime
+ * together with forced, a temperature that is not finite and > 0, top_k outside [0, bins]. */
+int vqa_prior_decode_primed(const vqa_prior_layer* layers, int depth, const float* x_embedding,
+                            const float* pos_embedding, const float* out_kernel, const float* out_bias,
+                            const float* ycond, const float* xcond, const int64_t* forced, float* logits,
+                            int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx, int width,
+                            int heads, int blocks, int bins, int out_ld, int64_t start, uint64_t seed,
+                            const int64_t* prime, int prime_len, float temperature, int top_k, vqa_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,9 @@
 Synthetic codes (uniform over the codebook), random-init weights. The cpu leg times the oracle's train step
 (oracle/prior_ref.py, torch CPU fp32) on a bounded sample.
     python tools/bench_prior.py [--batch 8] [--steps 10] [--samples 16] [--sample-len 2048] [--no-cpu]
+The sample leg takes the primed decode's options: --prime-len P (the first P positions are given, random codes;
+P = --sample-len times the primed positions alone, head skipped), --temperature, --top-k, and --repeats R (R timed
+launches in one process; ms_per_position is their median, ms_per_position_repeats lists them).
 """
 import argparse
 import json
@@ -30,6 +33,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--samples", type=int, default=16)
     ap.add_argument("--sample-len", type=int, default=2048)
+    ap.add_argument("--prime-len", type=int, default=0)
+    ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--only", default="")
@@ -134,15 +141,25 @@ def main():
                                                           residual_depth=8), dtype="fp32", device="cuda")
         g = torch.Generator(device=dev).manual_seed(2)
         up = torch.randint(0, a.bins - 1, (a.samples, a.ctx // 4), device=dev, generator=g)
-        m.sample(a.samples, max_length=16, x_cond=up, seed=1)  # warm-up (conditioner + decode)
+        prime = (torch.randint(0, a.bins - 1, (a.samples, a.prime_len), device=dev, generator=g)
+                 if a.prime_len else None)
+        opts = dict(prime=prime, temperature=a.temperature, top_k=a.top_k)
+        m.sample(a.samples, max_length=16, x_cond=up, seed=1, temperature=a.temperature,
+                 top_k=a.top_k)  # warm-up (conditioner + the decode kernel that is timed)
         torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out_tok = m.sample(a.samples, max_length=a.sample_len, x_cond=up, seed=2)
-        torch.cuda.synchronize()
-        el = time.perf_counter() - t0
+        els = []
+        for _ in range(max(1, a.repeats)):  # one window per launch; an error raises and ends the run
+            t0 = time.perf_counter()
+            out_tok = m.sample(a.samples, max_length=a.sample_len, x_cond=up, seed=2, **opts)
+            torch.cuda.synchronize()
+            els.append(time.perf_counter() - t0)
+        el = sorted(els)[len(els) // 2]
         print(json.dumps({"metric": "tokens/sec ancestral decode (upsampler prior + ConditionerNet)",
                           "value": round(a.samples * a.sample_len / el, 1), "unit": "tokens/s", "n_gpus": 1,
-                          "ms_per_position": round(el / a.sample_len * 1e3, 4), "samples": a.samples,
+                          "ms_per_position": round(el / a.sample_len * 1e3, 4),
+                          "ms_per_position_repeats": [round(e / a.sample_len * 1e3, 4) for e in els],
+                          "prime_len": a.prime_len, "temperature": a.temperature, "top_k": a.top_k,
+                          "samples": a.samples,
                           "positions": a.sample_len, "dtype": "fp32 (decode)",
                           "config": {"workload": "BASELINE config 5", "ctx": a.ctx, "bins": a.bins, **kw},
                           "tokens_in_range": bool(((out_tok >= 0) & (out_tok < a.bins)).all())}), flush=True)

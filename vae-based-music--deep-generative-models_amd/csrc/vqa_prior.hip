@@ -1524,6 +1524,13 @@ __global__ __launch_bounds__(256) void rowsum_final_kernel(const float* part, in
 // depth residual-attention blocks, the output head, z = logits + Gumbel(seed, sample, step, bin) and
 // next token = argmax z (RelaxedOneHotCategorical(1).sample() then argmax). fp32 throughout, weights fp32
 // from L2. Optional: forced input tokens (teacher-forced check) and per-step logits output.
+// A prime (vqa_prior_decode_primed) gives the first prime_len next-input tokens: those steps do everything up to
+// the output head (the caches and the LayerNorm ring must hold them) and run the head only when the logits are
+// asked for. The noise stays keyed by the absolute step, so priming a decode with its own first tokens
+// reproduces the rest bit for bit. kPrimed = true is the instantiation that knows the prime; without one the
+// step loop is the unprimed decode's. kFilter = true is the instantiation with a temperature and / or top-k
+// (score = logit / temperature + G over the bins whose logit is >= the k-th largest of the row); the default
+// (temperature 1, top-k off) runs kFilter = false, whose arithmetic is the unfiltered decode's.
 constexpr int kDecMaxLayers = 8;
 constexpr int kDecW = 128;   // model width
 constexpr int kDecAW = 32;   // attention width (m_attn 0.25)
@@ -1550,6 +1557,7 @@ struct DecArgs {
   const float* ycond;     // (N, W) or null
   const float* xcond;     // (N, T, W) fp32 or null
   const int64_t* forced;  // (N, steps + 1) or null
+  const int64_t* prime;   // (N, prime_len) or null: tokens[n][j] = prime[n][j - 1] for 1 <= j <= prime_len
   float* logits;          // (N, steps, bins) or null
   int64_t* tokens;        // (N, steps + 1)
   float* kc;              // (N, depth, T, 32) key cache
@@ -1559,6 +1567,9 @@ struct DecArgs {
   long long start;
   unsigned long long seed;
   float scale, emb_scale, eps;
+  int prime_len;          // 0 <= prime_len <= steps (0 without a prime)
+  int topk;               // 0: off, else 1 <= topk < bins (kFilter only)
+  float temp;             // temperature, finite and > 0 (kFilter only)
 };
 
 // y[o] = b[o] + sum_k x[k] W[k][o] (W row-major (K, O), O % 4 == 0): thread (4-output chunk c, k-group kg) sums
@@ -1645,6 +1656,58 @@ __global__ __launch_bounds__(256) void prior_decode_prep_kernel(DecArgs a) {
   }
 }
 
+// Order-preserving 32-bit key of a float (a larger float has a larger key; -0 < +0, NaNs at the two ends) and
+// its inverse.
+__device__ __forceinline__ unsigned dec_key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float dec_unkey(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+}
+
+// The k-th largest of v[0 .. n) (1 <= k <= n, n <= 2048, v in LDS), by all 256 threads: a radix select over the
+// keys, most significant byte first. Four rounds whatever the data (NaNs and all-equal rows are keys like any
+// other): a round counts, in hist[256], the byte of every key that matches the bytes chosen so far; wave 0 then
+// finds the byte value d with (#keys with a larger byte) < k <= (#keys with a byte >= d), which becomes the next
+// chosen byte, and k drops by the number of keys above it. The invariant 1 <= k <= #matching keys holds from
+// round to round, so one d always qualifies; sel is nevertheless preset so that a round can never leave it
+// unset. sel holds 2 ints. Ends with every thread holding the result; hist and sel are free again after the
+// caller's next barrier.
+__device__ float dec_kth_largest(const float* v, int n, int k, int* hist, int* sel) {
+  const int tid = threadIdx.x;
+  unsigned prefix = 0, mask = 0;
+#pragma unroll 1
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    hist[tid] = 0;
+    __syncthreads();
+    if (tid == 0) { sel[0] = 0; sel[1] = k; }
+    for (int e = tid; e < n; e += 256) {
+      const unsigned key = dec_key(v[e]);
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
+    }
+    __syncthreads();
+    if (tid < 64) {
+      // lane L holds the bytes 255 - 4L .. 252 - 4L, largest first; `above` = keys with a larger byte
+      int c[4], t = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { c[j] = hist[255 - 4 * tid - j]; t += c[j]; }
+      int above = xl::incl_scan(t) - t;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (above < k && k <= above + c[j]) { sel[0] = 255 - 4 * tid - j; sel[1] = k - above; }
+        above += c[j];
+      }
+    }
+    __syncthreads();
+    prefix |= (unsigned)sel[0] << shift;
+    mask |= 255u << shift;
+    k = sel[1];
+  }
+  return dec_unkey(prefix);
+}
+
+template <bool kPrimed, bool kFilter>
 __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
   __shared__ __attribute__((aligned(16))) float x[kDecW], x1[kDecW], hb[kDecW], r1[kDecW];
   __shared__ float ring[kDecMaxLayers][3][kDecW];
@@ -1655,6 +1718,7 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
   __shared__ float stat[4];
   __shared__ __attribute__((aligned(16))) float bestv[1024];
   __shared__ int besti[256];
+  __shared__ int ksel[2];
   const int n = blockIdx.x, tid = threadIdx.x;
   for (int e = tid; e < kDecMaxLayers * 3 * kDecW; e += 256) (&ring[0][0][0])[e] = 0.f;
   int64_t tok = a.start;
@@ -1767,15 +1831,34 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
       if (tid < kDecW) x[tid] = cat[tid] + x1[tid];
       __syncthreads();
     }
+    // a primed step: the next input is the prime's; its head runs only for the logits output
+    bool primed = false;
+    if constexpr (kPrimed) {
+      primed = i < a.prime_len;
+      if (primed && !a.logits) {
+        tok = a.prime[(size_t)n * a.prime_len + i];
+        if (tid == 0) a.tokens[(size_t)n * (a.steps + 1) + i + 1] = tok;
+        continue;
+      }
+    }
     // output head + Gumbel-max
     dec_matvec(x, kDecW, a.hw, a.hb, scr, a.ldo, bestv);  // scr holds the logits (ldo >= bins columns)
+    float thr = -INFINITY;  // top-k: only the bins with logit >= the k-th largest of the row take part
+    if constexpr (kFilter) {
+      if (a.topk > 0) thr = dec_kth_largest(scr, a.bins, a.topk, besti, ksel);
+    }
     float bv = -INFINITY;
     int bi = 0;
     for (int v = tid; v < a.bins; v += 256) {
       const float lg = scr[v];
       if (a.logits) a.logits[((size_t)n * a.steps + i) * a.bins + v] = lg;
+      if constexpr (kFilter) {
+        if (!(lg >= thr)) continue;
+      }
       const float u = prior_uniform(a.seed, (uint64_t)n, (uint64_t)i, (uint64_t)v);
-      const float z = lg + (-logf(-logf(u)));
+      float z;
+      if constexpr (kFilter) z = lg / a.temp + (-logf(-logf(u)));
+      else z = lg + (-logf(-logf(u)));
       if (z > bv) { bv = z; bi = v; }
     }
     __syncthreads();
@@ -1790,7 +1873,10 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
       }
       __syncthreads();
     }
-    const int64_t samp = besti[0];
+    int64_t samp = besti[0];
+    if constexpr (kPrimed) {
+      if (primed) samp = a.prime[(size_t)n * a.prime_len + i];
+    }
     if (tid == 0) a.tokens[(size_t)n * (a.steps + 1) + i + 1] = samp;
     tok = a.forced ? a.forced[(size_t)n * (a.steps + 1) + i + 1] : samp;
     __syncthreads();
@@ -2230,16 +2316,24 @@ extern "C" size_t vqa_prior_decode_cache_bytes(int N, int depth, int ctx) {
   return ((size_t)2 * N * depth * ctx * kDecAW + (size_t)depth * kDecComposed) * sizeof(float);
 }
 
-extern "C" int vqa_prior_decode(const vqa_prior_layer* layers, int depth, const float* x_embedding,
-                                const float* pos_embedding, const float* out_kernel, const float* out_bias,
-                                const float* ycond, const float* xcond, const int64_t* forced, float* logits,
-                                int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx, int width,
-                                int heads, int blocks, int bins, int out_ld, int64_t start, uint64_t seed,
-                                vqa_stream_t stream) {
+extern "C" int vqa_prior_decode_primed(const vqa_prior_layer* layers, int depth, const float* x_embedding,
+                                       const float* pos_embedding, const float* out_kernel, const float* out_bias,
+                                       const float* ycond, const float* xcond, const int64_t* forced, float* logits,
+                                       int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx,
+                                       int width, int heads, int blocks, int bins, int out_ld, int64_t start,
+                                       uint64_t seed, const int64_t* prime, int prime_len, float temperature,
+                                       int top_k, vqa_stream_t stream) {
   VQA_ARG(layers && x_embedding && pos_embedding && out_kernel && out_bias && tokens && cache && N > 0 && steps > 0 &&
               steps <= ctx && blocks > 0 && ctx % blocks == 0 && bins > 0 && out_ld >= bins && out_ld % 4 == 0 &&
               out_ld <= 2048,
           "prior_decode: bad arguments (bins %d, out_ld %d)", bins, out_ld);
+  // the prime, the temperature and top-k are settled here, before anything is launched
+  VQA_ARG(prime_len >= 0 && prime_len <= steps, "prior_decode: prime_len %d outside [0, steps %d]", prime_len, steps);
+  VQA_ARG(prime || prime_len == 0, "prior_decode: prime_len %d without a prime", prime_len);
+  VQA_ARG(!(prime && forced), "prior_decode: a prime and forced tokens are mutually exclusive");
+  VQA_ARG(std::isfinite(temperature) && temperature > 0.f, "prior_decode: temperature %g is not finite and > 0",
+          (double)temperature);
+  VQA_ARG(top_k >= 0 && top_k <= bins, "prior_decode: top_k %d outside [0, bins %d]", top_k, bins);
   VQA_REQUIRE(depth > 0 && depth <= kDecMaxLayers && width == kDecW && heads > 0 && kDecAW % heads == 0 &&
                   kDecAW / heads <= 32 && ctx / blocks <= kDecMaxL && heads <= 4,
               VQA_E_UNSUPPORTED, "prior_decode: depth %d width %d heads %d block %d unsupported", depth, width, heads,
@@ -2272,9 +2366,28 @@ extern "C" int vqa_prior_decode(const vqa_prior_layer* layers, int depth, const 
   a.scale = 1.0f / sqrtf((float)(kDecAW / heads));
   a.emb_scale = sqrtf((float)width);
   a.eps = 1e-6f;
+  a.prime = prime_len > 0 ? prime : nullptr;
+  a.prime_len = prime_len;
+  a.topk = (top_k > 0 && top_k < bins) ? top_k : 0;  // 0 and bins: every bin takes part
+  a.temp = temperature;
+  const bool filter = a.topk > 0 || temperature != 1.0f;
   hipLaunchKernelGGL(prior_decode_prep_kernel, dim3(64, depth), dim3(256), 0, (hipStream_t)stream, a);
   VQA_LAUNCHED("prior_decode_prep_kernel");
-  hipLaunchKernelGGL(prior_decode_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, a);
+  const bool primed = prime_len > 0;
+  void (*kern)(DecArgs) = primed ? (filter ? prior_decode_kernel<true, true> : prior_decode_kernel<true, false>)
+                                 : (filter ? prior_decode_kernel<false, true> : prior_decode_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3(N), dim3(256), 0, (hipStream_t)stream, a);
   VQA_LAUNCHED("prior_decode_kernel");
   return VQA_OK;
+}
+
+extern "C" int vqa_prior_decode(const vqa_prior_layer* layers, int depth, const float* x_embedding,
+                                const float* pos_embedding, const float* out_kernel, const float* out_bias,
+                                const float* ycond, const float* xcond, const int64_t* forced, float* logits,
+                                int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx, int width,
+                                int heads, int blocks, int bins, int out_ld, int64_t start, uint64_t seed,
+                                vqa_stream_t stream) {
+  return vqa_prior_decode_primed(layers, depth, x_embedding, pos_embedding, out_kernel, out_bias, ycond, xcond, forced,
+                                 logits, tokens, cache, cache_bytes, N, steps, ctx, width, heads, blocks, bins, out_ld,
+                                 start, seed, nullptr, 0, 1.0f, 0, stream);
 }

@@ -423,12 +423,32 @@ class FMHABasedAutoregressiveModel:
         return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
 
     def sample(self, n_samples, max_length=None, x_cond=None, y_cond=None, return_attention_weights=False, seed=0,
-               forced=None, return_logits=False):
+               forced=None, return_logits=False, prime=None, temperature=1.0, top_k=0):
         """autoregressive_fmha.py:162-240: (N, max_length + 1) int64 tokens starting with the start token, each
-        next token = argmax(logits + Gumbel noise). One persistent decode launch."""
+        next token = argmax(logits / temperature + Gumbel noise) over the top_k largest logits (0: all). One
+        persistent decode launch. prime (N, P <= max_length) int64: the tokens after the start token that are
+        given, not drawn (the codes a window of long-form sampling shares with the windows before it); the noise
+        is keyed by the absolute step, so a prime taken from an unprimed draw of the same seed reproduces it."""
         L = self.context_length if max_length is None else int(max_length)
         if not 0 < L <= self.context_length:
             raise ValueError(f"max_length {L} outside (0, {self.context_length}]")
+        temperature = float(temperature)
+        if not (math.isfinite(temperature) and temperature > 0.0):
+            raise ValueError(f"temperature {temperature} must be finite and > 0")
+        top_k = int(top_k)
+        if not 0 <= top_k <= self.bins:
+            raise ValueError(f"top_k {top_k} outside [0, {self.bins}]")
+        if prime is not None:
+            if forced is not None:
+                raise ValueError("prime and forced are mutually exclusive")
+            prime = torch.as_tensor(prime, device=self.device)
+            if prime.dtype != torch.int64:
+                raise ValueError(f"prime must be int64 (got {prime.dtype})")
+            if prime.dim() != 2 or prime.shape[0] != n_samples or prime.shape[1] > L:
+                raise ValueError(f"prime shape {tuple(prime.shape)}: expected ({n_samples}, <= {L})")
+            prime = prime.contiguous()
+            if prime.numel() and not (int(prime.min()) >= 0 and int(prime.max()) < self.bins):
+                raise ValueError(f"prime values outside [0, {self.bins})")
         why = V.decode_shape_error(self.context_length, self.heads, self.blocks)
         if why is not None:
             raise ValueError(f"sample(): {why}")
@@ -465,7 +485,8 @@ class FMHABasedAutoregressiveModel:
             ow, ob = owp, obp
         V.prior_decode(layers, self.store.view(self.emb_name), self._pos().contiguous(), ow, ob, tokens,
                        self.decode_cache(n_samples), L, self.context_length, self.heads, self.blocks,
-                       self.start_token, seed, ycond=yc, xcond=xc, forced=forced, logits=logits, bins=self.bins)
+                       self.start_token, seed, ycond=yc, xcond=xc, forced=forced, logits=logits, bins=self.bins,
+                       prime=prime, temperature=temperature, top_k=top_k)
         if return_logits:
             return tokens, logits
         if return_attention_weights:
@@ -853,9 +874,11 @@ class Prior:
         for t, acc in zip(self.metrics, ck["trackers"]):
             t._acc.copy_(acc.to(self.device))
 
-    def sample(self, n_samples, z_cond=None, y=None, return_attn_weights=False, seed=0):
+    def sample(self, n_samples, z_cond=None, y=None, return_attn_weights=False, seed=0, prime=None, temperature=1.0,
+               top_k=0):
         """prior.py:374-408: one window of n_ctx tokens, the start token first (as FMHABasedAutoregressiveModel.sample
-        returns it; VQVAESampler drops it). y: genre labels (N,) through the LabelConditioner."""
+        returns it; VQVAESampler drops it). y: genre labels (N,) through the LabelConditioner. prime, temperature,
+        top_k: as FMHABasedAutoregressiveModel.sample."""
         if z_cond is not None and int(z_cond.shape[0]) != n_samples:
             raise ValueError(f"Batch Size not matching, Expected:{n_samples}, Getting: {int(z_cond.shape[0])}")
         y_cond = None
@@ -867,4 +890,5 @@ class Prior:
                 raise ValueError(f"Batch Size not matching, Expected:{n_samples}, Getting: {y.numel()}")
             y_cond = self._label_embed(y)
         return self.prior.sample(n_samples, x_cond=z_cond, y_cond=y_cond, seed=seed,
-                                 return_attention_weights=return_attn_weights)
+                                 return_attention_weights=return_attn_weights, prime=prime, temperature=temperature,
+                                 top_k=top_k)

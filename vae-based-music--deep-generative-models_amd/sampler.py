@@ -5,6 +5,10 @@ upsampler, conditioned through its ConditionerNet on the level above) samples it
 just drawn above it. Each window is ONE persistent decode launch (Prior.sample -> vqa_prior_decode): the KV-cache
 kernel walks the positions on the device, so the whole multi-level draw is `levels` launches plus the
 conditioners' up-sampling — no per-token host round trip and no per-token graph replay.
+
+Long-form sampling (sample(total_length=...)): a level's codes are drawn in overlapping windows (window_starts);
+every window after the first is primed with the codes it shares with the windows before it
+(vqa_prior_decode_primed) and is still one launch.
 """
 from __future__ import annotations
 
@@ -46,21 +50,83 @@ class VQVAESampler:
                                      x_cond_kwargs=x_cond_kwargs, genre_classes=num_genres, dtype=dtype,
                                      device=device, seed=seed + l))
 
-    def sample(self, n_samples, y_genre=None, seed=0):
-        """Sampler.py:65-114: from the top level down; returns [zs_0, ..., zs_{L-1}], (n_samples, n_ctx_l) int64
-        codes without the start token. Level l draws its Gumbel noise with seed + l."""
+    def sample(self, n_samples, y_genre=None, seed=0, *, total_length=None, hop_lengths=None, temperature=1.0,
+               top_k=0):
+        """Sampler.py:65-114: from the top level down; returns [zs_0, ..., zs_{L-1}], (n_samples, codes_l) int64
+        codes without the start token.
+
+        total_length=None: one window per level (codes_l = n_ctx_l), level l drawing its Gumbel noise with
+        seed + l. Otherwise long-form sampling: total_length counts top-level codes (at least the top n_ctx) and
+        level l gets total_length * hop_top / hop_l codes, drawn in windows of n_ctx_l codes that start every
+        hop_lengths[l] codes (default n_ctx_l // 2; window_starts). Each window is one primed decode launch, see
+        sample_level. temperature / top_k: as FMHABasedAutoregressiveModel.sample, for every window."""
         dev = self.priors[0].device
         zs = [torch.zeros(n_samples, 0, dtype=torch.int64, device=dev) for _ in range(self.levels)]
+        totals, hops = self._plan(total_length, hop_lengths)
         for level in reversed(range(self.levels)):
-            pr = self.priors[level]
-            x_cond = pr.get_cond(zs, 0, pr.context_length)
-            seq = pr.sample(n_samples=n_samples, z_cond=x_cond, y=y_genre, seed=seed + level)
-            zs[level] = torch.cat([zs[level], seq[:, 1:]], dim=-1)  # the start token removed (Sampler.py:108)
+            zs = self.sample_level(zs, level, y_genre=y_genre, seed=seed, total_length=totals[level],
+                                   hop_length=hops[level], temperature=temperature, top_k=top_k)
         return zs
 
-    def sample_level(self, zs, level):
-        """Sampler.py:116-124 (a stub in the reference)."""
-        return NotImplementedError
+    def _plan(self, total_length, hop_lengths):
+        """(codes per level, hop per level) of a sample() call, checked before anything is drawn: every window
+        start and end of a conditioned level must fall on a code of the level above (Prior.get_cond)."""
+        n_ctxs = [pr.context_length for pr in self.priors]
+        if total_length is None:
+            if hop_lengths is not None:
+                raise ValueError("hop_lengths needs total_length")
+            return list(n_ctxs), list(n_ctxs)
+        top = self.levels - 1
+        total_length = int(total_length)
+        if total_length < n_ctxs[top]:
+            raise ValueError(f"total_length {total_length} is shorter than the top window of {n_ctxs[top]}")
+        hops = [max(1, c // 2) for c in n_ctxs] if hop_lengths is None else [int(h) for h in hop_lengths]
+        if len(hops) != self.levels:
+            raise ValueError(f"hop_lengths has {len(hops)} entries for {self.levels} levels")
+        totals = []
+        for l in range(self.levels):
+            # hop_lengths are cumulative products: the top level's is a multiple of every other
+            totals.append(total_length * int(self.hop_lengths[top]) // int(self.hop_lengths[l]))
+            self._check_windows(l, totals[l], hops[l])
+        return totals, hops
+
+    def _check_windows(self, level, total, hop):
+        n_ctx = self.priors[level].context_length
+        starts = window_starts(total, n_ctx, hop)  # raises ValueError for a bad total or hop
+        r = self.priors[level].prior.cond_downsample_rate
+        if level != self.levels - 1 and r:
+            bad = [v for v in [hop, n_ctx] + starts if v % r]
+            if bad:
+                raise ValueError(f"level {level}: hop {hop}, window {n_ctx} and every window start must be multiples "
+                                 f"of the conditioning rate {r} (got {bad[0]})")
+        return starts
+
+    def sample_level(self, zs, level, y_genre=None, seed=0, total_length=None, hop_length=None, temperature=1.0,
+                     top_k=0):
+        """Sampler.py:116-124 (a stub in the reference): draw level `level` given the levels above it in zs and
+        return zs with that level filled. total_length: this level's codes (default one window), hop_length: the
+        distance of its window starts (default n_ctx // 2).
+
+        Window w at start s (window_starts) is one persistent decode launch: primed with the codes already drawn
+        in [s, s + n_ctx), conditioned on get_cond(zs, s, s + n_ctx), the label embedding at its position 0 as in
+        a training window, its noise seeded seed + level + levels * w (window 0 keeps the one-window seed). Only
+        the codes past the prime are appended. A failed launch raises; no later window is queued."""
+        pr = self.priors[level]
+        n_ctx = pr.context_length
+        total = n_ctx if total_length is None else int(total_length)
+        hop = max(1, n_ctx // 2) if hop_length is None else int(hop_length)
+        starts = self._check_windows(level, total, hop)
+        n_samples = zs[level].shape[0]
+        z = zs[level][:, :0]
+        zs = list(zs)
+        for w, s in enumerate(starts):
+            prime = z[:, s:] if z.shape[1] > s else None
+            x_cond = pr.get_cond(zs, s, s + n_ctx)
+            seq = pr.sample(n_samples=n_samples, z_cond=x_cond, y=y_genre, seed=seed + level + self.levels * w,
+                            prime=prime, temperature=temperature, top_k=top_k)
+            z = torch.cat([z, seq[:, 1 + z.shape[1] - s:]], dim=-1)  # start token and prime removed
+        zs[level] = z
+        return zs
 
 
 def window_starts(total_length, n_ctx, hop_length) -> List[int]:

@@ -42,7 +42,7 @@ EXPORTED = [
     "vqa_seqlin_fwd", "vqa_seqlin_prep", "vqa_seqlin_fwd_prepped", "vqa_seqlin_fwd_ln_prepped", "vqa_seqlin_wgrad_workspace", "vqa_seqlin_wgrad", "vqa_prior_embed_fwd", "vqa_colsum",
     "vqa_axpy", "vqa_dropout", "vqa_scale_f32", "vqa_tf_mix", "vqa_attn_fwd", "vqa_attn_bwd", "vqa_head_wt",
     "vqa_head_fwd", "vqa_head_bwd_workspace", "vqa_head_bwd", "vqa_rowsum_workspace", "vqa_rowsum", "vqa_prior_decode_cache_bytes",
-    "vqa_prior_decode",
+    "vqa_prior_decode", "vqa_prior_decode_primed",
 ]
 
 
@@ -142,6 +142,7 @@ _SIGS = {
     "vqa_rowsum": (_I, [_P, _L, _L, _F, _P, _P, _S, _P]),
     "vqa_prior_decode_cache_bytes": (_S, [_I, _I, _I]),
     "vqa_prior_decode": (_I, [_P, _I] + [_P] * 10 + [_S] + [_I] * 8 + [_L, _U, _P]),
+    "vqa_prior_decode_primed": (_I, [_P, _I] + [_P] * 10 + [_S] + [_I] * 8 + [_L, _U, _P, _I, _F, _I, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -752,12 +753,23 @@ def decode_shape_error(ctx, heads, blocks) -> Optional[str]:
 
 
 def prior_decode(layers, emb, pos, out_w, out_b, tokens, cache, steps, ctx, heads, blocks, start, seed, ycond=None,
-                 xcond=None, forced=None, logits=None, bins=None):
-    """out_w (width, ld) / out_b (ld,) with ld a multiple of 4 >= bins (zero-padded columns are never sampled)."""
+                 xcond=None, forced=None, logits=None, bins=None, prime=None, temperature=1.0, top_k=0):
+    """out_w (width, ld) / out_b (ld,) with ld a multiple of 4 >= bins (zero-padded columns are never sampled).
+    prime (N, P) int64: the first P next-input tokens (vqa_prior_decode_primed, include/vqa.h); temperature and
+    top_k as there. The defaults run the unfiltered kernel."""
     N = tokens.shape[0]
     bins = out_w.shape[1] if bins is None else int(bins)
     arr = (PriorLayerDesc * len(layers))(*layers)
-    _check(lib().vqa_prior_decode(arr, len(layers), ptr(emb), ptr(pos), ptr(out_w), ptr(out_b), ptr(ycond),
-                                  ptr(xcond), ptr(forced), ptr(logits), ptr(tokens), ptr(cache), cache.numel(), N,
-                                  steps, ctx, emb.shape[1], heads, blocks, bins, out_w.shape[1], start, seed, stream()),
-           "vqa_prior_decode")
+    prime_len = 0
+    if prime is not None:
+        if prime.dtype != torch.int64 or prime.dim() != 2 or prime.shape[0] != N:
+            raise VQAError(f"prime must be ({N}, P) int64 (got {tuple(prime.shape)} {prime.dtype})")
+        prime_len = int(prime.shape[1])
+        if prime_len == 0:
+            prime = None
+    _check(lib().vqa_prior_decode_primed(arr, len(layers), ptr(emb), ptr(pos), ptr(out_w), ptr(out_b), ptr(ycond),
+                                         ptr(xcond), ptr(forced), ptr(logits), ptr(tokens), ptr(cache),
+                                         cache.numel(), N, steps, ctx, emb.shape[1], heads, blocks, bins,
+                                         out_w.shape[1], start, seed, ptr(prime), prime_len, float(temperature),
+                                         int(top_k), stream()),
+           "vqa_prior_decode_primed")
