@@ -260,6 +260,43 @@ int vqa_synthetic_batch(float* x, int B, int64_t T, uint64_t seed, int rank, flo
 /* *counter += delta on the stream (graph-capturable step counters). */
 int vqa_counter_add(int64_t* counter, int64_t delta, vqa_stream_t stream);
 
+/* ---- device-resident corpus feed (replaces the host chunk feed of data_utils.py:65-206 — splitsongs /
+ *      split_convert / read_data — and the notebooks' shuffled tf.data pipeline) --------------------------
+ * The corpus is every track's PCM back to back in device memory (int16 or fp32, `pcm`) with a window table:
+ * starts[i] = the first sample of window i, labels[i] its class (labels may be NULL), i in [0, M). One launch
+ * writes this rank's batch of one step:
+ *   g = step + (counter ? *counter : 0)        (the counter is read on the device: a captured launch advances
+ *                                               with it — vqa_counter_add after each step)
+ *   S = M / (B*world)                          steps per epoch; the remainder of an epoch is dropped
+ *   epoch = g / S, pos = g % S
+ *   item b of this rank takes slot k = (pos*world + rank)*B + b
+ *   its window is i = perm(k) with shuffle, where perm is the keyed bijection of the dead-code reset under the
+ *   key (seed, epoch, VQA_FEED_PERM_LEVEL) — the host computes the same value as
+ *   vqa_reset_perm_index applied to (seed, epoch, VQA_FEED_PERM_LEVEL, M, k) — and i = k without
+ *   x[b][t]       = corpus[starts[i] + t] * 2^-15   (VQA_PCM_I16; exact in fp32)
+ *                 = corpus[starts[i] + t]           (VQA_PCM_F32)                x is (B, T) fp32
+ *   labels_out[b] = labels[i]                       (nullable)
+ *   index_out[b]  = i                               (nullable)
+ * So within one epoch every window is used at most once across all ranks, and different epochs use different
+ * permutations.
+ * Memory contract: the caller guarantees that `corpus` (16-byte aligned) is readable up to corpus_len samples
+ * rounded up to a multiple of 16 bytes. The kernel reads a window through aligned 16-byte loads of the chunks
+ * that enclose it and touches nothing outside that range. Each chosen window is checked once per item on the
+ * device: 0 <= starts[i] and starts[i] + T <= corpus_len; a window that fails is written as zeros with
+ * index_out[b] = -1 and is never read.
+ * VQA_E_INVALID_ARG before any launch (messages start "corpus_batch:"): a null corpus, starts or x; B, T or M not
+ * positive (B at most 65535); world < 1; rank outside [0, world); M < B*world; pcm not one of the two values;
+ * corpus not 16-byte aligned (x needs only a float's alignment: the rows' 16-byte stores are aligned by a scalar
+ * head and tail, whatever T is); labels_out without labels; a negative step or corpus_len. */
+enum { VQA_PCM_I16 = 0, VQA_PCM_F32 = 1 };
+#define VQA_FEED_PERM_LEVEL 0x46454544 /* the `level` of the permutation key for the feed's shuffle */
+int64_t vqa_corpus_steps_per_epoch(int64_t M, int B, int world); /* M / (B*world); host only */
+int vqa_corpus_batch(const void* corpus, int64_t corpus_len, int pcm, const int64_t* starts,
+                     const int64_t* labels /* may be NULL */, int64_t M, float* x,
+                     int64_t* labels_out /* may be NULL */, int64_t* index_out /* may be NULL */, int B, int64_t T,
+                     uint64_t seed, const int64_t* counter /* may be NULL */, int64_t step, int rank, int world,
+                     int shuffle, vqa_stream_t stream);
+
 /* ---- multi-resolution spectral loss --------------------------------------------------------------
  * Replaces vqvae.py:309-326 (_multispectral_loss) over data_utils.py:25-30 (spectral = |tf.signal.stft|)
  * and data_utils.py:33-40 (norm = tf.norm 'fro'), plus its GradientTape backward (vqvae.py:143):

@@ -1,4 +1,4 @@
-"""Spectral-loss helpers and the synthetic device feed — the hot-path part of the reference data_utils.py.
+"""Spectral-loss helpers, the audio loaders and the synthetic device feed of the reference data_utils.py.
 
 data_utils.py:19-22  STFT_ARGS (n_fft, hop_length, window_size) per resolution
 data_utils.py:25-30  spectral = |tf.signal.stft(x, frame_length=win, frame_step=hop, fft_length=n_fft)|
@@ -8,11 +8,20 @@ The STFT, the loss and its gradient run in libvqa's spectral kernels (csrc/vqa_s
 FFTs with TF framing — no centering, frame t = x[t*hop : t*hop+win] times a periodic Hann window, rfft
 zero-padded at the end to n_fft).
 
-File decoding (librosa / GTZAN, data_utils.py:43-206) is out of scope: the north star trains on
-synthetic chunks. `synthetic_batch_device` generates them in HBM with a HIP kernel (the
-device feed); `synthetic_batch` is the numpy restatement the tests and the oracle use.
+data_utils.py:43-238  load_audio, splitsongs, split_convert, read_data, generate_genre_samples: a folder of
+genre-labelled WAVs turned into training windows and labels, with the reference's names, arguments and result
+shapes. Files are integer-PCM WAV read with the standard library (no librosa: nothing is resampled, a file whose
+rate is not the requested one is an error) and the stratified split is a deterministic one of our own (no sklearn).
+These build host arrays, as the reference does; training itself reads a device-resident corpus through
+audio_feed.AudioCorpus / AudioFeed (one gather kernel per step inside the step's graph).
+
+`synthetic_batch_device` generates synthetic chunks in HBM with a HIP kernel; `synthetic_batch` is
+the numpy restatement the tests and the oracle use.
 """
 from __future__ import annotations
+
+import os
+import wave
 
 import numpy as np
 import torch
@@ -95,8 +104,9 @@ def splitsongs(X, y, window=0.05, overlap=0.5):
     """data_utils.py:65-91: a song cut into overlapping chunks of int(T * window) samples, hopping by
     int(chunk * (1 - overlap)); a chunk that would run past the end is dropped. X is (T,) or (C, T); returns
     ((n, chunk) or (n, C, chunk), (n,) copies of the label) — channels first, as the reference's callers then
-    transpose to (B, T, C). Host numpy, like the reference (the training feed itself is generated on the
-    device: synthetic_batch_device)."""
+    transpose to (B, T, C). Host numpy, like the reference. The device feed cuts its windows by the same rule
+    (audio_feed.window_starts) but keeps only their start offsets: the samples stay in one device tensor and a
+    step's windows are gathered by vqa_corpus_batch."""
     X = np.asarray(X)
     T = X.shape[-1]
     chunk = int(T * window)
@@ -104,6 +114,156 @@ def splitsongs(X, y, window=0.05, overlap=0.5):
     pieces = [X[..., s:s + chunk] for s in range(0, T - chunk + hop, hop)]
     pieces = [p for p in pieces if p.shape[-1] == chunk]
     return np.array(pieces), np.array([y] * len(pieces))
+
+
+SAMPLE_RATE = 3000
+
+# the GTZAN genre folders in the reference's label order (data_utils.py:13-16)
+IDX_TO_GENRES = dict(enumerate(("metal", "disco", "classical", "rock", "jazz", "country", "pop", "blues", "reggae",
+                                "hiphop")))
+GENRES = {name: idx for idx, name in IDX_TO_GENRES.items()}
+
+# data_utils.py:161: the one GTZAN file that does not decode
+SKIP_FILES = ("jazz/jazz.00054.wav",)
+
+SPLIT_PERM_LEVEL = 0x53504C54  # the `level` of the permutation key of stratified_split
+
+
+def read_wav_pcm(file, sr=None, offset=0.0, duration=None):
+    """Integer-PCM WAV -> (frames (n, C) integers as stored, bits per sample, sample rate). 8-bit samples are
+    returned with their 128 offset removed (int16), 16-bit as int16, 24- and 32-bit as int32. `offset` and
+    `duration` are seconds, cut to whole frames as int(seconds * rate). Raises ValueError for a WAV that is not
+    integer PCM (float, compressed) and, with `sr`, for a file of another rate: nothing is resampled."""
+    try:
+        w = wave.open(str(file), "rb")
+    except wave.Error as e:
+        raise ValueError(f"{file}: not an integer-PCM WAV ({e})") from None
+    with w:
+        rate, C, width, total = w.getframerate(), w.getnchannels(), w.getsampwidth(), w.getnframes()
+        if w.getcomptype() != "NONE" or width not in (1, 2, 3, 4):
+            raise ValueError(f"{file}: not an integer-PCM WAV (compression {w.getcomptype()}, {8 * width} bit)")
+        if sr is not None and int(sr) != rate:
+            raise ValueError(f"{file}: sample rate {rate} Hz, requested {int(sr)} Hz (files are not resampled)")
+        first = min(total, max(0, int(offset * rate)))
+        n = total - first if duration is None else min(total - first, max(0, int(duration * rate)))
+        w.setpos(first)
+        raw = w.readframes(n)
+    n = len(raw) // (width * C)  # a truncated file gives the frames it has
+    raw = raw[:n * width * C]
+    if width == 1:
+        a = np.frombuffer(raw, np.uint8).astype(np.int16) - 128
+    elif width == 2:
+        a = np.frombuffer(raw, "<i2")
+    elif width == 4:
+        a = np.frombuffer(raw, "<i4")
+    else:  # 24 bit: three little-endian bytes into the top of an int32, shifted down with the sign
+        b = np.frombuffer(raw, np.uint8).reshape(-1, 3).astype(np.uint32)
+        a = ((b[:, 0] << 8) | (b[:, 1] << 16) | (b[:, 2] << 24)).view(np.int32) >> 8
+    return a.reshape(n, C), 8 * width, rate
+
+
+def load_audio(file, sr=22050, offset=0.0, duration=None, mono=False):
+    """data_utils.py:43-48 (librosa.load there): -> (C, n) float32, a sample being int / 2^(bits-1) (8-bit data is
+    unsigned with a 128 offset), exactly for up to 24 bits. Integer-PCM WAV of 8, 16, 24 or 32 bits through the
+    standard library's `wave`; `mono` averages the channels; `offset` / `duration` are seconds. There is no
+    resampling: a file whose rate is not `sr` raises ValueError (naming both rates), as does a non-PCM WAV."""
+    a, bits, _ = read_wav_pcm(file, sr=sr, offset=offset, duration=duration)
+    x = (a.astype(np.float64) / float(1 << (bits - 1))).T  # (C, n)
+    if mono:
+        x = x.mean(axis=0, keepdims=True)
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def stratified_split(labels, test_fraction, seed=42):
+    """Deterministic stratified split -> (train indices, test indices), both ascending. Every class gives
+    floor(n_c * test_fraction + 0.5) of its n_c members to the test side (at least one and at most n_c - 1 when
+    n_c >= 2 and the fraction is positive; a class of one stays in train). The members picked are the first of the
+    class under the library's keyed permutation (vqa_reset_perm_index with key (seed, class rank,
+    SPLIT_PERM_LEVEL)). This is NOT sklearn's train_test_split partition: the reference's split depends on numpy's
+    global generator, ours only on the arguments."""
+    labels = np.asarray(labels)
+    classes, inv = np.unique(labels, return_inverse=True)
+    test = []
+    for c in range(len(classes)):
+        members = np.nonzero(inv == c)[0]
+        n = len(members)
+        k = 0
+        if test_fraction > 0 and n >= 2:
+            k = min(max(int(np.floor(n * float(test_fraction) + 0.5)), 1), n - 1)
+        test.extend(int(members[V.reset_perm_index(int(seed), c, SPLIT_PERM_LEVEL, n, j)]) for j in range(k))
+    test = np.array(sorted(test), dtype=np.int64)
+    train = np.setdiff1d(np.arange(len(labels), dtype=np.int64), test)
+    return train, test
+
+
+def split_convert(X, y, sample_rate=3000, duration=30, max_signal_len=660000, split_window=1.0, split_overlap=0.0):
+    """data_utils.py:100-136: every file of X loaded (load_audio, `duration` seconds, cut to max_signal_len
+    samples) and cut by splitsongs -> (waves (n, C, chunk) float32, genres (n,), file labels (n,) — the file's
+    base name repeated for each of its chunks)."""
+    arr_waves, arr_genres, arr_file_label = [], [], []
+    for fn, genre in zip(X, y):
+        file_label = str(fn).split('/')[-1]
+        signal = load_audio(fn, sr=sample_rate, duration=duration)[:, :max_signal_len]
+        signals, ys = splitsongs(signal, genre, window=split_window, overlap=split_overlap)
+        arr_waves.extend(signals)
+        arr_genres.extend(ys)
+        arr_file_label.extend([file_label] * len(ys))
+    return np.array(arr_waves), np.array(arr_genres), np.array(arr_file_label)
+
+
+def list_genre_files(src_dir, genres, max_files_per_genre=1000):
+    """The file walk of read_data (data_utils.py:152-168): for every genre of `genres` (a name -> label dict) the
+    files under src_dir/<genre>, in sorted order so that the result does not depend on the file system, at most
+    max_files_per_genre per folder, without SKIP_FILES -> (file names, labels)."""
+    arr_fn, arr_genres = [], []
+    for name, label in genres.items():
+        folder = os.path.join(src_dir, name)
+        for root, subdirs, files in sorted(os.walk(folder)):
+            for file in sorted(files)[:max_files_per_genre]:
+                file_name = os.path.join(root, file).replace(os.sep, "/")
+                if any(file_name.endswith(s) for s in SKIP_FILES):
+                    continue
+                arr_fn.append(file_name)
+                arr_genres.append(label)
+    return arr_fn, arr_genres
+
+
+def read_data(src_dir, genres, test_data_percentage=0.1, sample_rate=22050, duration=30, split_window=1.0,
+              split_overlap=0.0, max_signal_len=660000, shuffle_after_split=False, max_files_per_genre=1000,
+              random_state=42):
+    """data_utils.py:146-206 -> (X_train, y_train, y_file_train, X_test, y_test, y_file_test), X (n, C, chunk)
+    float32. The files are split into train and test stratified by genre and each side is then loaded and cut
+    (split_convert); with shuffle_after_split all files are cut first and the chunks are split stratified by file.
+    The split is stratified_split with `random_state` as its seed (the reference's 42): deterministic, but not
+    sklearn's partition."""
+    arr_fn, arr_genres = list_genre_files(src_dir, genres, max_files_per_genre)
+    kw = dict(sample_rate=sample_rate, duration=duration, max_signal_len=max_signal_len, split_window=split_window,
+              split_overlap=split_overlap)
+    if shuffle_after_split:
+        X, y, y_file = split_convert(arr_fn, arr_genres, **kw)
+        tr, te = stratified_split(y_file, test_data_percentage, random_state)
+        return X[tr], y[tr], y_file[tr], X[te], y[te], y_file[te]
+    tr, te = stratified_split(arr_genres, test_data_percentage, random_state)
+    X_test, y_test, y_file_test = split_convert([arr_fn[i] for i in te], [arr_genres[i] for i in te], **kw)
+    X_train, y_train, y_file_train = split_convert([arr_fn[i] for i in tr], [arr_genres[i] for i in tr], **kw)
+    return X_train, y_train, y_file_train, X_test, y_test, y_file_test
+
+
+def generate_genre_samples(X, y, return_genre=False):
+    """data_utils.py:209-238: one sample per genre, the first of X carrying each label 0 .. n_classes-1, stacked
+    -> (n_classes, ...); with return_genre also the labels (n_classes,)."""
+    y = np.asarray(y)
+    n_classes = len(np.unique(y))
+    first = []
+    for i in range(n_classes):
+        hits = np.where(y == i)[0]
+        if len(hits) == 0:
+            raise ValueError(f"labels must be 0 .. {n_classes - 1}: none is {i}")
+        first.append(int(hits[0]))
+    train_samples = np.stack([X[j] for j in first], axis=0)
+    if return_genre:
+        return train_samples, np.arange(n_classes)
+    return train_samples
 
 
 def synthetic_batch(B: int, T: int, sr: int = 44100, seed: int = 1234) -> np.ndarray:

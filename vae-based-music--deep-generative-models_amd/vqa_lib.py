@@ -43,6 +43,7 @@ EXPORTED = [
     "vqa_axpy", "vqa_dropout", "vqa_scale_f32", "vqa_tf_mix", "vqa_attn_fwd", "vqa_attn_bwd", "vqa_head_wt",
     "vqa_head_fwd", "vqa_head_bwd_workspace", "vqa_head_bwd", "vqa_rowsum_workspace", "vqa_rowsum", "vqa_prior_decode_cache_bytes",
     "vqa_prior_decode", "vqa_prior_decode_primed",
+    "vqa_corpus_steps_per_epoch", "vqa_corpus_batch",
 ]
 
 
@@ -143,6 +144,9 @@ _SIGS = {
     "vqa_prior_decode_cache_bytes": (_S, [_I, _I, _I]),
     "vqa_prior_decode": (_I, [_P, _I] + [_P] * 10 + [_S] + [_I] * 8 + [_L, _U, _P]),
     "vqa_prior_decode_primed": (_I, [_P, _I] + [_P] * 10 + [_S] + [_I] * 8 + [_L, _U, _P, _I, _F, _I, _P]),
+    # device-resident corpus feed
+    "vqa_corpus_steps_per_epoch": (_L, [_L, _I, _I]),
+    "vqa_corpus_batch": (_I, [_P, _L, _I, _P, _P, _L, _P, _P, _P, _I, _L, _U, _P, _L, _I, _I, _I, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -499,6 +503,47 @@ def layernorm_bwd(x, dy, gamma, dx, dgamma, dbeta, eps, deferred=None):
 
 def counter_add(counter, delta=1):
     _check(lib().vqa_counter_add(ptr(counter), delta, stream()), "vqa_counter_add")
+
+
+PCM_I16, PCM_F32 = 0, 1  # VQA_PCM_*
+FEED_PERM_LEVEL = 0x46454544  # VQA_FEED_PERM_LEVEL: the `level` of the feed's shuffle key
+
+
+def corpus_steps_per_epoch(M: int, B: int, world: int = 1) -> int:
+    """Full steps in one epoch of M windows, M // (B*world) (vqa_corpus_steps_per_epoch; host only)."""
+    return int(lib().vqa_corpus_steps_per_epoch(int(M), int(B), int(world)))
+
+
+def corpus_batch(corpus, corpus_len, starts, labels, x, labels_out=None, index_out=None, seed=0, counter=None,
+                 step=0, rank=0, world=1, shuffle=True):
+    """One step's batch of a device-resident corpus (vqa_corpus_batch, include/vqa.h): corpus is the 1-D int16 or
+    fp32 sample tensor (allocated up to a multiple of 16 bytes past corpus_len samples), starts / labels the (M,)
+    int64 window table, x the (B, T) or (B, T, 1) fp32 batch; labels_out / index_out (B,) int64."""
+    if corpus.dtype == torch.int16:
+        pcm = PCM_I16
+    elif corpus.dtype == torch.float32:
+        pcm = PCM_F32
+    else:
+        raise VQAError(f"corpus_batch: the corpus is int16 or float32 (got {corpus.dtype})")
+    if x.dtype != torch.float32:
+        raise VQAError("corpus_batch fills an fp32 tensor")
+    if starts.dtype != torch.int64 or any(t is not None and t.dtype != torch.int64
+                                         for t in (labels, labels_out, index_out, counter)):
+        raise VQAError("corpus_batch: starts, labels, labels_out, index_out and counter are int64")
+    corpus_len = int(corpus_len)
+    if (corpus_len * corpus.element_size() + 15) // 16 * 16 > corpus.numel() * corpus.element_size():
+        raise VQAError(f"corpus_batch: the corpus tensor ({corpus.numel()} samples) does not cover corpus_len "
+                       f"{corpus_len} rounded up to 16 bytes")
+    M = starts.numel()
+    if labels is not None and labels.numel() != M:
+        raise VQAError(f"corpus_batch: {labels.numel()} labels for {M} windows")
+    B, T = x.shape[0], x.numel() // x.shape[0]
+    for t in (labels_out, index_out):
+        if t is not None and t.numel() != B:
+            raise VQAError(f"corpus_batch: labels_out / index_out hold {B} entries")
+    _check(lib().vqa_corpus_batch(ptr(corpus), corpus_len, pcm, ptr(starts), ptr(labels), M, ptr(x), ptr(labels_out),
+                                  ptr(index_out), B, T, int(seed), ptr(counter), int(step), int(rank), int(world),
+                                  int(bool(shuffle)), stream()), "vqa_corpus_batch")
 
 
 def _int_array(vals):

@@ -16,7 +16,9 @@ each level runs forward then backward immediately (levels are independent), so o
 activations are alive. Weights, gradients and the codebook EMA sums are flat fp32 buffers: the whole
 data-parallel exchange sums [grads | EMA sums | reset rows | losses] over ranks: on RCCL per level as soon as that
 level's backward ends (`overlap_exchange`, vqa_dp.level_regions) or as ONE all_reduce after the join (default).
-`capture_train_step` records the full step as a hipGraph (torch.cuda.graph) so replay has no host cost.
+`capture_train_step` records the full step as a hipGraph (torch.cuda.graph) so replay has no host cost; given an
+audio_feed.AudioFeed instead of a batch, the graph also holds the feed's gather launch and its step counter's
+increment, so a replay trains on the next batch of the device-resident corpus with no copy at all.
 """
 from __future__ import annotations
 
@@ -29,6 +31,7 @@ import torch
 
 import vqa_dp
 import vqa_lib as V
+from audio_feed import AudioFeed
 from data_utils import SpectralTarget, multispectral_loss_and_grad
 from encdec import Decoder, Encoder
 from vqa_layers import CKPT_VERSION, ParamStore, checkpoint_layout
@@ -193,6 +196,7 @@ class VQVAE:
         self.vqvaes = [LevelModel(self.input_shape, self.encoders[l], self.decoders[l], self.vqs[l], l, owner=self)
                        for l in range(levels)]
         self._graph = None
+        self._graph_feed = None  # the AudioFeed a captured step draws from (None: it copies the caller's batch in)
         # run the levels' independent forward/backward chains on one stream each (VQA_LEVEL_STREAMS=0: serial)
         self.concurrent_levels = os.environ.get("VQA_LEVEL_STREAMS", "1") != "0"
         self._streams = None
@@ -208,6 +212,7 @@ class VQVAE:
         self.optimizer.build(self.store)
         self._graph = None
         self._graph_pool = None
+        self._graph_feed = None
 
     @property
     def metrics(self):
@@ -401,8 +406,16 @@ class VQVAE:
         """vqvae.py:111-146. Returns the running-mean metric dict (0-dim device tensors)."""
         if self.optimizer is None:
             self.compile()
+        if isinstance(data, AudioFeed):
+            # the step captured with this very feed draws its batch inside the graph; any other feed (or the same
+            # one after a change of seed, which the graph's launch does not see) is drawn here and runs eagerly
+            if self._graph is not None and data is self._graph_feed and data.seed == self._graph_feed_seed:
+                self._replay()
+                return self.results()
+            data = data.next()
         x = self._as_input(data)
-        if self._graph is not None and x.shape == self._graph_x.shape:
+        # a graph captured with a feed overwrites its input with the feed's batch: other data runs eagerly
+        if self._graph is not None and self._graph_feed is None and x.shape == self._graph_x.shape:
             self._graph_x.copy_(x)
             self._replay()
             return self.results()
@@ -412,8 +425,9 @@ class VQVAE:
         return self.results()
 
     def test_step(self, data):
-        """vqvae.py:148-172 — forward + losses; the VQ EMA runs (reference default training=True)."""
-        x = self._as_input(data)
+        """vqvae.py:148-172 — forward + losses; the VQ EMA runs (reference default training=True). An AudioFeed
+        gives its next batch."""
+        x = self._as_input(data.next() if isinstance(data, AudioFeed) else data)
         with torch.no_grad():
             self._compute(x, training_grads=False)
             self._exchange(grads=False)
@@ -423,7 +437,8 @@ class VQVAE:
     def evaluate(self, x=None, y=None, batch_size=None, verbose=0, steps=None, return_dict=False, **kwargs):
         """keras Model.evaluate over test_step (vqvae.py:148-172), as src/callback/vae_monitor.py:69 calls it on
         the validation dataset: metrics reset, test_step per batch (the codebook EMA runs, VectorQuantizer.py:75),
-        the running means returned (vqa_module.keras_evaluate)."""
+        the running means returned (vqa_module.keras_evaluate). An AudioFeed is such a dataset: one epoch of its
+        batches."""
         return keras_evaluate(self, x, y, batch_size=batch_size, verbose=verbose, steps=steps,
                               return_dict=return_dict)
 
@@ -432,15 +447,27 @@ class VQVAE:
         """Run `warmup` eager steps (real steps) then record one full train step as a hipGraph; later
         train_step calls with this batch shape copy the batch in and replay. With a process group the
         step is two graphs around the eager RCCL all_reduce; with `overlap_exchange` on a device-side backend
-        (RCCL) the per-level collectives are captured with the step into one graph."""
+        (RCCL) the per-level collectives are captured with the step into one graph.
+        x_example may be an audio_feed.AudioFeed: its gather launch and counter increment are then recorded at the
+        head of the graph and the graph's input is the feed's own buffer (no copy); the warm-up steps draw (and
+        consume) feed steps, and a later train_step(feed) with this feed replays."""
         if self.optimizer is None:
             self.compile()
-        x = self._as_input(x_example)
-        self._graph_x = x.clone()
+        feed = x_example if isinstance(x_example, AudioFeed) else None
+        if feed is not None:
+            self._graph_x = self._as_input(feed.x)
+            if self._graph_x.data_ptr() != feed.x.data_ptr():
+                raise ValueError("the feed's batch buffer must be on the model's device")
+        else:
+            self._graph_x = self._as_input(x_example).clone()
+        self._graph = None
+        self._graph_feed, self._graph_feed_seed = feed, (feed.seed if feed is not None else None)
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
             for _ in range(warmup):
+                if feed is not None:
+                    feed.next()
                 self._compute(self._graph_x, True)
                 self._exchange()
                 self._update(True)
@@ -452,6 +479,8 @@ class VQVAE:
         self._graph_pool = torch.cuda.graph_pool_handle()
         g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1, pool=self._graph_pool, capture_error_mode="thread_local"):
+            if feed is not None:
+                feed.next()
             self._compute(self._graph_x, True)
             one_graph = self._overlapped or not vqa_dp.active(self.process_group)
             if self._overlapped:
@@ -547,9 +576,20 @@ class VQVAE:
     # ------------------------------------------------------------------ training loop / state
     def fit(self, x=None, y=None, batch_size=32, epochs=1, shuffle=True, seed=0, verbose=0):
         """Minimal keras fit: `self.metrics` reset per epoch (keras semantics); returns the history of
-        epoch-end results."""
+        epoch-end results. With an audio_feed.AudioFeed as x an epoch is the feed's steps_per_epoch steps (graph
+        replays once the step is captured with that feed); batch size, shuffling and seed are the feed's."""
         if self.optimizer is None:
             self.compile()
+        if isinstance(x, AudioFeed):
+            hist = []
+            for ep in range(epochs):
+                self.reset_metrics()
+                for _ in range(x.steps_per_epoch):
+                    self.train_step(x)
+                hist.append({k: float(v) for k, v in self.results().items()})
+                if verbose:
+                    print(f"epoch {ep + 1}/{epochs}", hist[-1])
+            return hist
         xs = np.asarray(x, np.float32)
         n = xs.shape[0]
         rng = np.random.default_rng(seed)
