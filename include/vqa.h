@@ -130,6 +130,37 @@ int vqa_conv1d_bwd_data_weight(const void* dy, const float* w, const void* x, co
 size_t vqa_conv1d_bwd_data_weight_workspace(int B, int T_in, int T_out, int C_in, int C_out, int K, int stride,
                                             int dilation, int pad_left, int flags, int dtype);
 
+/* ---- which kernel a conv call runs. Host-only: no GPU is touched, no pointer is read.
+ * The kernel of every entry point above is chosen on the host from the shape, dtype and flags.
+ * vqa_conv1d_route answers, from the very functions the entry points launch from, what a call with these
+ * arguments would run: it returns a VQA_ROUTE_* family (>= 0) and fills detail[VQA_ROUTE_DETAIL] (nullable)
+ * with the template parameters that vary, or returns the VQA_E_* code (< 0) the call itself would return
+ * before launching anything. Arguments are those of the entry point `op` names (the transposed ops ignore
+ * `dilation`); the kernel pointer is taken to be 16-byte aligned (any allocation is).
+ *   CONV32        detail = {O, PVX, NEP, FW}       32-channel kernel: x chunks per thread, epilogue tensors,
+ *                                                   1 with the fused weight gradient
+ *   GATHER_MFMA   detail = {C, O, PV, TM, NEP}     C / O of the gather (O is doubled by the PAIR layout of
+ *                                                   Conv1DTranspose fwd and the stride-2 data gradient)
+ *   CO1           detail = {C}                     one-output-channel kernels
+ *   CI1           detail = {O, KT}                 one-input-channel kernel
+ *   THIN_O        detail = {C};  THIN  detail = {OV};  DIRECT  detail = {C, O} (generic VALU kernel)
+ *   WGRAD_MFMA    detail = {C, O, TT};  WGRAD_THIN  detail = {C, O, wide side is x};  WGRAD_DIRECT  {C, O, TT}
+ *   TWO_CALL      vqa_conv1d_bwd_data_weight as vqa_conv1d_bwd_data + vqa_conv1d_bwd_weight:
+ *                 detail = {family of the data gradient, family of the weight gradient}
+ * A change to a dispatch threshold shows here, so a test can pin the kernel it means to check. */
+enum {
+  VQA_OP_FWD = 0, VQA_OP_BWD_DATA = 1, VQA_OP_BWD_WEIGHT = 2, VQA_OP_BWD_DATA_WEIGHT = 3,
+  VQA_OP_T_FWD = 4, VQA_OP_T_BWD_DATA = 5, VQA_OP_T_BWD_WEIGHT = 6
+};
+enum {
+  VQA_ROUTE_CO1 = 0, VQA_ROUTE_CONV32 = 1, VQA_ROUTE_GATHER_MFMA = 2, VQA_ROUTE_CI1 = 3, VQA_ROUTE_THIN_O = 4,
+  VQA_ROUTE_THIN = 5, VQA_ROUTE_DIRECT = 6, VQA_ROUTE_WGRAD_MFMA = 7, VQA_ROUTE_WGRAD_THIN = 8,
+  VQA_ROUTE_WGRAD_DIRECT = 9, VQA_ROUTE_TWO_CALL = 10
+};
+#define VQA_ROUTE_DETAIL 8
+int vqa_conv1d_route(int op, int B, int T_in, int T_out, int C_in, int C_out, int K, int stride, int dilation,
+                     int pad_left, int flags, int dtype, int* detail);
+
 /* ---- fused residual block: replaces resnet.py:7-29 ResnetConv1DBlock (C = 32):
  *      h = conv_a(relu(x)) + b_a (k3, dilation), y = x + conv_b(relu(h)) + b_b (k3, dilation 1), SAME padding.
  * Weights in Keras layout (3, C, C). The forward keeps h on chip; h_out (nullable) receives relu(h).

@@ -39,6 +39,19 @@ CONFIGS = {
                                        dilation_factor=3), B=2),
 }
 
+# Architectures other than the reference's default (width 32, depth <= 4), for the teacher-forced tests only (the
+# end-to-end oracle runs over CONFIGS gain nothing from them): they run the unfused Python fallbacks.
+FALLBACK_CONFIGS = {
+    # w64: residual width 64 -> no fused residual block, no fused decoder tail; convs 64 -> 64 (K 3 and the K 4
+    # stride-2 down / transposed up convs)
+    "w64": dict(cfg=R.RefConfig(input_len=2048, levels=2, latent_dim=64, down_depth=[2, 1], strides=[2, 2],
+                                num_embeddings=256, residual_width=64, residual_depth=2, dilation_factor=3), B=2),
+    # deep: dilations 1 .. 243; the blocks at dilation >= 81 are unfused inside an otherwise fused stack
+    "deep": dict(cfg=R.RefConfig(input_len=4096, levels=1, latent_dim=64, down_depth=[2], strides=[2],
+                                 num_embeddings=256, residual_width=32, residual_depth=6, dilation_factor=3), B=1),
+}
+ALL_CONFIGS = {**CONFIGS, **FALLBACK_CONFIGS}
+
 
 def _model(cfg, B, dtype, params, vq):
     m = VQVAE((cfg.input_len, 1), cfg.levels, cfg.latent_dim, cfg.down_depth, cfg.strides,
@@ -499,13 +512,15 @@ def test_repeated_step_bitwise(cuda):
     assert runs[0][2] == runs[1][2]
 
 
-@pytest.mark.parametrize("name", ["cfg1", "tiny"])
+@pytest.mark.parametrize("name", ["cfg1", "tiny", "w64", "deep"])
 def test_resblock_backward_teacher_forced(cuda, name):
     """Every residual block's backward (resnet.py:7-29) on the GPU vs fp64 autograd of the same block,
-    fed the GPU's own saved input and upstream gradient, with ReLU masks taken from the GPU activations."""
+    fed the GPU's own saved input and upstream gradient, with ReLU masks taken from the GPU activations.
+    A block ran fused exactly where vqa_resblock_supported says so (w64: nowhere; deep: below dilation 81)."""
     import torch.nn.functional as F
     import resnet
-    c = CONFIGS[name]
+    import vqa_lib as V
+    c = ALL_CONFIGS[name]
     cfg, B = c["cfg"], c["B"]
     params, vq = R.init_params(cfg, 1), R.init_vq_state(cfg, 2)
     m = _model(cfg, B, "fp32", params, vq)
@@ -535,6 +550,8 @@ def test_resblock_backward_teacher_forced(cuda, name):
     for rec in log:
         blk = rec["blk"]
         na, nb = blk.conv_a.name, blk.conv_b.name
+        assert rec["fused"] == V.resblock_supported(cfg.residual_width, blk.dilation, V.F32), \
+            f"{na}: fused={rec['fused']} at width {cfg.residual_width}, dilation {blk.dilation}"
         W = {k: torch.tensor(params[k], dtype=torch.float64, requires_grad=True)
              for k in (f"{na}/kernel", f"{na}/bias", f"{nb}/kernel", f"{nb}/bias")}
         xv = rec["x"].clone().requires_grad_(True)
@@ -626,12 +643,13 @@ def _spy_convs(monkeypatch):
     return log
 
 
-@pytest.mark.parametrize("name,dtype", [("cfg1", "fp32"), ("tiny", "fp32"), ("cfg2_short", "fp32")])
+@pytest.mark.parametrize("name,dtype", [("cfg1", "fp32"), ("tiny", "fp32"), ("cfg2_short", "fp32"), ("w64", "fp32"),
+                                        ("deep", "fp32")])
 def test_every_conv_call_teacher_forced(cuda, monkeypatch, name, dtype):
     """Every conv kernel call of a real train step (forward, data-gradient, weight-gradient; fused ReLU,
     residual and ReLU' masks) against fp64 autograd of the oracle's TF-semantics conv on the SAME
     inputs and masks the GPU used. No branch can flip, so the bound is strict (relative L2 1e-5)."""
-    c = CONFIGS[name]
+    c = ALL_CONFIGS[name]
     cfg, B = c["cfg"], c["B"]
     params, vq = R.init_params(cfg, 1), R.init_vq_state(cfg, 2)
     m = _model(cfg, B, dtype, params, vq)

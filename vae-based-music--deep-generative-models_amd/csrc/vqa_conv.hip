@@ -39,6 +39,9 @@ struct GatherArgs {
   // wpart receives one fp32 partial [K*O*C dW | C db] per workgroup, wrelu: dW uses relu(u)
   float* wpart = nullptr;
   int wrelu = 0;
+  // generic kernel only: take the weights rounded to bf16, as the MFMA kernels stage them (run_gather sets it for
+  // the all-bf16 convs whose channel counts the MFMA kernel serves and whose tile is too large for it)
+  int wbf16 = 0;
 };
 
 __device__ __forceinline__ float weff(const GatherArgs& a, int k, int c, int o) {
@@ -69,12 +72,18 @@ __device__ __forceinline__ int bias_index(const GatherArgs& a, int o) {
 
 // ------------------------------------------------------------------------------------------------
 // Generic VALU gather conv: any C/O/K/S/D, mixed fp32/bf16 ends. Used for the 1-channel layers at
-// the waveform ends (first encoder conv C=1, decoder output conv O=1 and its data-gradient).
+// the waveform ends (first encoder conv C=1, decoder output conv O=1 and its data-gradient), and as the
+// fall-through for 32- / 64-channel tiles too large for the MFMA kernel's stager or LDS. Such a bf16 conv takes
+// its weights rounded to bf16 (a.wbf16), as the MFMA kernels stage them: which of the two kernels it runs depends
+// on its epilogue flags, and its result must not (bf16 x bf16 products are exact in fp32; only the order of the
+// fp32 sum differs).
+
 template <class TX, class TY>
 __global__ __launch_bounds__(256) void gather_direct_kernel(GatherArgs a) {
   const TX* X = (const TX*)a.x;
   const long long total = (long long)a.B * a.T_out * a.O;
   const bool relu = a.flags & VQA_PRE_RELU;
+  const bool wb = a.wbf16;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (long long)gridDim.x * blockDim.x) {
     const int o = (int)(e % a.O);
@@ -89,7 +98,8 @@ __global__ __launch_bounds__(256) void gather_direct_kernel(GatherArgs a) {
       for (int c = 0; c < a.C; ++c) {
         float xv = ld(xr + c);
         if (relu) xv = fmaxf(xv, 0.f);
-        acc += xv * weff(a, k, c, o);
+        const float w = weff(a, k, c, o);
+        acc += xv * (wb ? (float)(bf16)w : w);
       }
     }
     const long long oi = out_index(a, n, t, o);
@@ -1528,43 +1538,75 @@ static int gather_nep(const GatherArgs& a, bool fw) {
   return (((a.flags & VQA_POST_MASK) || fw) ? 1 : 0) + ((a.flags & VQA_ADD_RESIDUAL) ? 1 : 0);
 }
 
-template <class T, int C, int O, int TM>
-static int launch_gather_mfma_t(const GatherArgs& a, hipStream_t s) {
-  constexpr int XS = C + lds_pad<T>(), WS = C + lds_pad<T>();
-  const int rows_in = (TM - 1) * a.S + (a.K - 1) * a.D + 1;
-  const int nep = gather_nep(a, false);
-  const size_t ebytes = (size_t)TM * O * sizeof(T);
-  const size_t lds = ((size_t)a.K * O * WS + (size_t)rows_in * XS) * sizeof(T) + 2 * ebytes;
-  VQA_REQUIRE(lds <= 160 * 1024, VQA_E_UNSUPPORTED, "gather conv: LDS tile too large (%zu B)", lds);
+// What the MFMA gather kernel needs for one launch, from the shape alone (no HIP call): the tile rows, the 16-byte
+// chunks per thread of the register stager (PV: 3, 4, 5, 8 or 12) and the dynamic LDS. ok = false: this conv does
+// not run on the MFMA kernel (run_gather then takes the next kernel down the list).
+struct MfmaPlan {
+  bool ok;
+  int tm, pv, nep;
+  size_t lds;
+};
+
+// channel counts and taps the MFMA kernel is built for (its tap loop is unrolled for K <= 4)
+static bool mfma_channels(const GatherArgs& a) {
+  return a.K <= 4 && (a.C == 32 || a.C == 64) && (a.O == 32 || a.O == 64 || a.O == 128);
+}
+
+static MfmaPlan mfma_plan(const GatherArgs& a, int dtype) {
+  MfmaPlan p{};
+  if ((uintptr_t)a.w & 15) return p;  // stage_weights reads the kernel in 16-byte vectors
+  if (a.flags & (VQA_X_F32 | VQA_Y_F32)) return p;
+  if (!mfma_channels(a)) return p;
+  p.tm = gather_tm(a.O, a.S);
+  p.nep = gather_nep(a, false);
+  const int rows_in = (p.tm - 1) * a.S + (a.K - 1) * a.D + 1;
+  const int esz = dtype == VQA_BF16 ? 2 : 4;
   // 16-byte chunks per tile held in registers per thread; a tile only a few chunks over a multiple of
   // 256 must not pay for the next size up
-  const long long chunks = (long long)rows_in * C * sizeof(T) / 16 + (long long)nep * TM * O * sizeof(T) / 16;
+  const long long chunks = (long long)rows_in * a.C * esz / 16 + (long long)p.nep * p.tm * a.O * esz / 16;
+  if (chunks > 12 * 256) return p;
+  if ((size_t)rows_in * (a.C + 8) * 4 + (size_t)a.K * a.O * (a.C + 8) * 4 > 150 * 1024) return p;
+  // the kernel's own LDS: weights, input rows (row pitch C + 16 bytes) and the two epilogue-operand tiles. A tile
+  // that does not fit (fp32 C = 64 -> O = 128: the width-64 transposed conv and stride-2 data gradient) is not an
+  // MFMA conv
+  const int pitch = a.C + 16 / esz;
+  p.lds = ((size_t)a.K * a.O * pitch + (size_t)rows_in * pitch) * esz + 2 * (size_t)p.tm * a.O * esz;
+  if (p.lds > 160 * 1024) return p;
   const int pv = (int)((chunks + 255) / 256);
-  if (pv <= 3) return launch_gather_mfma_pv<T, C, O, TM, 3>(a, lds, s);
-  if (pv <= 4) return launch_gather_mfma_pv<T, C, O, TM, 4>(a, lds, s);
-  if (pv <= 5) return launch_gather_mfma_pv<T, C, O, TM, 5>(a, lds, s);
-  if (pv <= 8) return launch_gather_mfma_pv<T, C, O, TM, 8>(a, lds, s);
-  if (pv <= 12) return launch_gather_mfma_pv<T, C, O, TM, 12>(a, lds, s);
-  vqa::set_error("gather conv: tile of %lld chunks exceeds the register stager", chunks);
-  return VQA_E_UNSUPPORTED;
+  p.pv = pv <= 3 ? 3 : (pv <= 4 ? 4 : (pv <= 5 ? 5 : (pv <= 8 ? 8 : 12)));
+  p.ok = true;
+  return p;
+}
+
+template <class T, int C, int O, int TM>
+static int launch_gather_mfma_t(const GatherArgs& a, const MfmaPlan& p, hipStream_t s) {
+  static_assert(C + lds_pad<T>() == C + 16 / (int)sizeof(T), "mfma_plan's row pitch");
+  VQA_REQUIRE(p.ok && p.tm == TM, VQA_E_UNSUPPORTED, "gather conv: no MFMA plan for this tile");
+  switch (p.pv) {
+    case 3: return launch_gather_mfma_pv<T, C, O, TM, 3>(a, p.lds, s);
+    case 4: return launch_gather_mfma_pv<T, C, O, TM, 4>(a, p.lds, s);
+    case 5: return launch_gather_mfma_pv<T, C, O, TM, 5>(a, p.lds, s);
+    case 8: return launch_gather_mfma_pv<T, C, O, TM, 8>(a, p.lds, s);
+    default: return launch_gather_mfma_pv<T, C, O, TM, 12>(a, p.lds, s);
+  }
 }
 
 template <class T, int C, int O>
-static int launch_gather_mfma_o(const GatherArgs& a, hipStream_t s) {
-  if constexpr (O == 32) return launch_gather_mfma_t<T, C, O, 128>(a, s);
-  else return launch_gather_mfma_t<T, C, O, 64>(a, s);
+static int launch_gather_mfma_o(const GatherArgs& a, const MfmaPlan& p, hipStream_t s) {
+  if constexpr (O == 32) return launch_gather_mfma_t<T, C, O, 128>(a, p, s);
+  else return launch_gather_mfma_t<T, C, O, 64>(a, p, s);
 }
 
 template <class T>
-static int launch_gather_mfma(const GatherArgs& a, hipStream_t s) {
+static int launch_gather_mfma(const GatherArgs& a, const MfmaPlan& p, hipStream_t s) {
   if (a.C == 32) {
-    if (a.O == 32) return launch_gather_mfma_o<T, 32, 32>(a, s);
-    if (a.O == 64) return launch_gather_mfma_o<T, 32, 64>(a, s);
-    if (a.O == 128) return launch_gather_mfma_o<T, 32, 128>(a, s);
+    if (a.O == 32) return launch_gather_mfma_o<T, 32, 32>(a, p, s);
+    if (a.O == 64) return launch_gather_mfma_o<T, 32, 64>(a, p, s);
+    if (a.O == 128) return launch_gather_mfma_o<T, 32, 128>(a, p, s);
   } else if (a.C == 64) {
-    if (a.O == 32) return launch_gather_mfma_o<T, 64, 32>(a, s);
-    if (a.O == 64) return launch_gather_mfma_o<T, 64, 64>(a, s);
-    if (a.O == 128) return launch_gather_mfma_o<T, 64, 128>(a, s);
+    if (a.O == 32) return launch_gather_mfma_o<T, 64, 32>(a, p, s);
+    if (a.O == 64) return launch_gather_mfma_o<T, 64, 64>(a, p, s);
+    if (a.O == 128) return launch_gather_mfma_o<T, 64, 128>(a, p, s);
   }
   vqa::set_error("gather conv: no MFMA tile for C=%d O=%d", a.C, a.O);
   return VQA_E_UNSUPPORTED;
@@ -1643,19 +1685,6 @@ static int launch_conv32(const GatherArgs& a, int pvx, hipStream_t s, int* nwg_o
   }
 }
 
-static bool mfma_ok(const GatherArgs& a, int dtype) {
-  if ((uintptr_t)a.w & 15) return false;  // stage_weights reads the kernel in 16-byte vectors
-  if (a.flags & (VQA_X_F32 | VQA_Y_F32)) return false;
-  if (a.K > 4) return false;  // the kernel's tap loop is unrolled for K <= 4
-  if (!((a.C == 32 || a.C == 64) && (a.O == 32 || a.O == 64 || a.O == 128))) return false;
-  const int tm = gather_tm(a.O, a.S);
-  const int rows_in = (tm - 1) * a.S + (a.K - 1) * a.D + 1;
-  const int esz = dtype == VQA_BF16 ? 2 : 4;
-  const long long chunks = (long long)rows_in * a.C * esz / 16 + (long long)gather_nep(a, false) * tm * a.O * esz / 16;
-  if (chunks > 12 * 256) return false;
-  return (size_t)rows_in * (a.C + 8) * 4 + (size_t)a.K * a.O * (a.C + 8) * 4 <= 150 * 1024;
-}
-
 template <class TX, class TY>
 static int launch_gather_direct(const GatherArgs& a, hipStream_t s) {
   const long long total = (long long)a.B * a.T_out * a.O;
@@ -1685,9 +1714,12 @@ static int launch_gather_thinO(const GatherArgs& a, hipStream_t s) {
   return a.C == 32 ? launch_gather_thinO_c<TX, TY, 32>(a, s) : launch_gather_thinO_c<TX, TY, 64>(a, s);
 }
 
+// the thin kernel indexes its (row, channel group) items with 32-bit integers
+static bool gather_thin_fits(const GatherArgs& a) { return (long long)a.B * a.T_out * a.O < (1ll << 31); }
+
 template <class TX, class TY>
 static int launch_gather_thin(const GatherArgs& a, hipStream_t s) {
-  VQA_REQUIRE((long long)a.B * a.T_out * a.O < (1ll << 31), VQA_E_UNSUPPORTED, "thin conv: tensor too large");
+  VQA_REQUIRE(gather_thin_fits(a), VQA_E_UNSUPPORTED, "thin conv: tensor too large");
   const int OV = (a.O % 8 == 0) ? 8 : 1;
   const long long total = (long long)a.B * a.T_out * (a.O / OV);
   long long blocks = (total + 255) / 256;
@@ -1795,43 +1827,85 @@ static bool ci1_ok(const GatherArgs& a) {
          (size_t)((CI1_RB - 1) * a.S + (a.K - 1) * a.D + 1) * sizeof(float) <= 64 * 1024;
 }
 
-int run_gather(const GatherArgs& a, int dtype, hipStream_t s) {
+// Which kernel a gather conv runs, decided on the host from the shape, dtype and flags alone (no HIP call): the
+// one list run_gather launches from and vqa_conv1d_route reports from.
+enum { G_CONV32, G_MFMA, G_CI1, G_THINO, G_THIN, G_DIRECT };
+struct GatherRoute {
+  int family;
+  int pvx;     // G_CONV32: x chunks per thread
+  MfmaPlan m;  // G_MFMA
+};
+
+static GatherRoute gather_route(const GatherArgs& a, int dtype) {
+  GatherRoute r{};
+  if ((r.pvx = conv32_pvx(a, dtype, false))) {
+    r.family = G_CONV32;
+    return r;
+  }
+  r.m = mfma_plan(a, dtype);
+  if (r.m.ok) {
+    r.family = G_MFMA;
+  } else if (ci1_ok(a)) {
+    r.family = G_CI1;
+  } else if (a.O <= 8 && (a.C == 32 || a.C == 64) && a.wmode != W_PAIR && a.K <= 4 && a.S <= 2 && a.D <= 64) {
+    r.family = G_THINO;
+  } else if ((a.C <= 8 || a.O <= 8) && (size_t)a.K * a.C * a.O * 4 <= 64 * 1024 &&
+             (a.wmode != W_PAIR || (a.O / 2) % 8 == 0 || a.O % 8 != 0)) {
+    r.family = G_THIN;
+  } else {
+    r.family = G_DIRECT;
+  }
+  return r;
+}
+
+// the shape checks of every gather conv (pointers apart)
+static int gather_check(const GatherArgs& a, int dtype) {
   VQA_ARG(dtype == VQA_F32 || dtype == VQA_BF16, "unknown dtype %d", dtype);
-  VQA_ARG(a.x && a.w && a.y, "null tensor pointer");
   VQA_ARG(a.B > 0 && a.T_in > 0 && a.T_out > 0 && a.C > 0 && a.O > 0 && a.K > 0 && a.S > 0 && a.D > 0,
           "non-positive shape");
+  return VQA_OK;
+}
+
+int run_gather(const GatherArgs& a, int dtype, hipStream_t s) {
+  const int rc = gather_check(a, dtype);
+  if (rc != VQA_OK) return rc;
+  VQA_ARG(a.x && a.w && a.y, "null tensor pointer");
   VQA_ARG(!(a.flags & VQA_POST_MASK) || a.mask, "VQA_POST_MASK without mask");
   VQA_ARG(!(a.flags & VQA_ADD_RESIDUAL) || a.resid, "VQA_ADD_RESIDUAL without residual");
-  if (const int pvx = conv32_pvx(a, dtype, false)) {
-    return dtype == VQA_BF16 ? launch_conv32<bf16, false>(a, pvx, s, nullptr)
-                             : launch_conv32<float, false>(a, pvx, s, nullptr);
-  }
-  if (mfma_ok(a, dtype)) return dtype == VQA_BF16 ? launch_gather_mfma<bf16>(a, s) : launch_gather_mfma<float>(a, s);
+  const GatherRoute r = gather_route(a, dtype);
   const bool xf = dtype == VQA_F32 || (a.flags & VQA_X_F32);
   const bool yf = dtype == VQA_F32 || (a.flags & VQA_Y_F32);
-  if (ci1_ok(a)) {
-    if (xf && yf) return launch_gather_ci1<float, float>(a, s);
-    if (xf) return launch_gather_ci1<float, bf16>(a, s);
-    if (yf) return launch_gather_ci1<bf16, float>(a, s);
-    return launch_gather_ci1<bf16, bf16>(a, s);
+  switch (r.family) {
+    case G_CONV32:
+      return dtype == VQA_BF16 ? launch_conv32<bf16, false>(a, r.pvx, s, nullptr)
+                               : launch_conv32<float, false>(a, r.pvx, s, nullptr);
+    case G_MFMA:
+      return dtype == VQA_BF16 ? launch_gather_mfma<bf16>(a, r.m, s) : launch_gather_mfma<float>(a, r.m, s);
+    case G_CI1:
+      if (xf && yf) return launch_gather_ci1<float, float>(a, s);
+      if (xf) return launch_gather_ci1<float, bf16>(a, s);
+      if (yf) return launch_gather_ci1<bf16, float>(a, s);
+      return launch_gather_ci1<bf16, bf16>(a, s);
+    case G_THINO:
+      if (xf && yf) return launch_gather_thinO<float, float>(a, s);
+      if (xf) return launch_gather_thinO<float, bf16>(a, s);
+      if (yf) return launch_gather_thinO<bf16, float>(a, s);
+      return launch_gather_thinO<bf16, bf16>(a, s);
+    case G_THIN:
+      if (xf && yf) return launch_gather_thin<float, float>(a, s);
+      if (xf) return launch_gather_thin<float, bf16>(a, s);
+      if (yf) return launch_gather_thin<bf16, float>(a, s);
+      return launch_gather_thin<bf16, bf16>(a, s);
+    default:
+      if (xf && yf) return launch_gather_direct<float, float>(a, s);
+      if (xf) return launch_gather_direct<float, bf16>(a, s);
+      if (yf) return launch_gather_direct<bf16, float>(a, s);
+      {
+        GatherArgs b = a;
+        b.wbf16 = mfma_channels(a) ? 1 : 0;
+        return launch_gather_direct<bf16, bf16>(b, s);
+      }
   }
-  if (a.O <= 8 && (a.C == 32 || a.C == 64) && a.wmode != W_PAIR && a.K <= 4 && a.S <= 2 && a.D <= 64) {
-    if (xf && yf) return launch_gather_thinO<float, float>(a, s);
-    if (xf) return launch_gather_thinO<float, bf16>(a, s);
-    if (yf) return launch_gather_thinO<bf16, float>(a, s);
-    return launch_gather_thinO<bf16, bf16>(a, s);
-  }
-  if ((a.C <= 8 || a.O <= 8) && (size_t)a.K * a.C * a.O * 4 <= 64 * 1024 &&
-      (a.wmode != W_PAIR || (a.O / 2) % 8 == 0 || a.O % 8 != 0)) {
-    if (xf && yf) return launch_gather_thin<float, float>(a, s);
-    if (xf) return launch_gather_thin<float, bf16>(a, s);
-    if (yf) return launch_gather_thin<bf16, float>(a, s);
-    return launch_gather_thin<bf16, bf16>(a, s);
-  }
-  if (xf && yf) return launch_gather_direct<float, float>(a, s);
-  if (xf) return launch_gather_direct<float, bf16>(a, s);
-  if (yf) return launch_gather_direct<bf16, float>(a, s);
-  return launch_gather_direct<bf16, bf16>(a, s);
 }
 
 // ---- weight gradient planning ----
@@ -1886,6 +1960,21 @@ static WgradPlan plan_wgrad(int dtype, int B, int T_in, int T_out, int C, int O,
   p.E = K * C * O + p.nb;
   p.ws_bytes = (size_t)p.nwg * p.E * sizeof(float);
   return p;
+}
+
+// The plan of a weight gradient and the checks it must pass before anything is launched (no HIP call): what
+// run_wgrad launches from and vqa_conv1d_route reports from.
+static int wgrad_route(WgradPlan* out, int dtype, int B, int T_in, int T_out, int C, int O, int K, int S, int D,
+                       int flags) {
+  VQA_ARG(dtype == VQA_F32 || dtype == VQA_BF16, "unknown dtype %d", dtype);
+  VQA_ARG(B > 0 && T_in > 0 && T_out > 0 && C > 0 && O > 0 && K > 0 && S > 0 && D > 0, "non-positive shape");
+  const WgradPlan p = plan_wgrad(dtype, B, T_in, T_out, C, O, K, S, D, flags);
+  *out = p;
+  VQA_REQUIRE(p.lds <= 150 * 1024, VQA_E_UNSUPPORTED, "wgrad: LDS tile too large (%zu B)", p.lds);
+  VQA_REQUIRE(p.kind != WG_DIRECT || K * C * O <= 16 * 256 * 64, VQA_E_UNSUPPORTED,
+              "wgrad: generic path limited to K*C*O<=262144");
+  VQA_REQUIRE(p.nb <= 256 && 256 % p.nb == 0, VQA_E_UNSUPPORTED, "wgrad: bias width must divide 256");
+  return VQA_OK;
 }
 
 template <class T, int C, int O, int TT>
@@ -1951,19 +2040,14 @@ static int launch_wgrad_thin_t(const WgradArgs& a, const WgradPlan& p, bool xf, 
 int run_wgrad(const void* x, const void* g, float* dw, float* db, int B, int T_in, int T_out, int C, int O, int K,
               int S, int D, int P, int flags, int dtype, void* ws, size_t ws_bytes, hipStream_t s,
               vqa_partials_desc* defer) {
-  VQA_ARG(dtype == VQA_F32 || dtype == VQA_BF16, "unknown dtype %d", dtype);
   VQA_ARG(x && g && dw, "null tensor pointer");
-  VQA_ARG(B > 0 && T_in > 0 && T_out > 0 && C > 0 && O > 0 && K > 0 && S > 0 && D > 0, "non-positive shape");
-  WgradPlan p = plan_wgrad(dtype, B, T_in, T_out, C, O, K, S, D, flags);
+  WgradPlan p{};
+  int rc = wgrad_route(&p, dtype, B, T_in, T_out, C, O, K, S, D, flags);
+  if (rc != VQA_OK) return rc;
   VQA_ARG(ws && ws_bytes >= p.ws_bytes, "workspace too small: need %zu bytes, got %zu", p.ws_bytes, ws_bytes);
-  VQA_REQUIRE(p.lds <= 150 * 1024, VQA_E_UNSUPPORTED, "wgrad: LDS tile too large (%zu B)", p.lds);
-  VQA_REQUIRE(p.kind != WG_DIRECT || K * C * O <= 16 * 256 * 64, VQA_E_UNSUPPORTED,
-              "wgrad: generic path limited to K*C*O<=262144");
-  VQA_REQUIRE(p.nb <= 256 && 256 % p.nb == 0, VQA_E_UNSUPPORTED, "wgrad: bias width must divide 256");
   WgradArgs a{x, g, (float*)ws, B, T_in, T_out, C, O, K, S, D, P, p.CH, p.nchunk, flags, p.nb};
   const bool xf = dtype == VQA_F32 || (flags & VQA_X_F32);
   const bool gf = dtype == VQA_F32 || (flags & VQA_Y_F32);
-  int rc;
   switch (p.kind) {
     case WG_MFMA:
       rc = dtype == VQA_BF16 ? launch_wgrad_mfma<bf16>(a, p, s) : launch_wgrad_mfma<float>(a, p, s);
@@ -2011,6 +2095,63 @@ extern "C" int vqa_same_pad_left(int T_in, int K, int stride, int dilation) {
   return pad / 2;
 }
 
+// ---- the gather each conv entry point runs (the entry points launch it, vqa_conv1d_route reports its kernel)
+static GatherArgs conv_fwd_gather(const void* x, const float* w, const float* bias, const void* residual, void* y,
+                                  int B, int T_in, int T_out, int C_in, int C_out, int K, int stride, int dilation,
+                                  int pad_left, int flags) {
+  return GatherArgs{x, w, bias, residual, nullptr, y, B, T_in, T_out, C_in, C_out, K, stride, dilation, pad_left,
+                    W_DIRECT, K, 0, T_out, flags & (VQA_PRE_RELU | VQA_ADD_RESIDUAL | VQA_X_F32 | VQA_Y_F32)};
+}
+
+// flags for the data-gradient gather: the gather input is dy (y side), output dx (x side)
+static int swap_xy_flags(int flags) {
+  int f = flags & (VQA_POST_MASK | VQA_ADD_RESIDUAL);
+  if (flags & VQA_X_F32) f |= VQA_Y_F32;
+  if (flags & VQA_Y_F32) f |= VQA_X_F32;
+  return f;
+}
+
+static int conv_bwd_data_gather(GatherArgs* out, const void* dy, const float* w, const void* mask,
+                                const void* residual, void* dx, int B, int T_in, int T_out, int C_in, int C_out,
+                                int K, int stride, int dilation, int pad_left, int flags) {
+  const int f = swap_xy_flags(flags);
+  if (stride == 1) {
+    *out = GatherArgs{dy, w, nullptr, residual, mask, dx, B, T_out, T_in, C_out, C_in, K, 1, dilation,
+                      (K - 1) * dilation - pad_left, W_FLIP_T, K, 0, T_in, f};
+    return VQA_OK;
+  }
+  VQA_REQUIRE(stride == 2 && K == 4 && dilation == 1 && pad_left == 1, VQA_E_UNSUPPORTED,
+              "conv1d_bwd_data: strided data-gradient supports stride 2, K 4, pad_left 1 (got s=%d K=%d d=%d p=%d)",
+              stride, K, dilation, pad_left);
+  *out = GatherArgs{dy, w, nullptr, residual, mask, dx, B, T_out, T_out, C_out, 2 * C_in, 3, 1, 1, 1,
+                    W_PAIR, K, pad_left, T_in, f};
+  return VQA_OK;
+}
+
+static int convT_check(int K, int stride, int pad_left) {
+  VQA_REQUIRE(stride == 2 && K == 4 && pad_left == 1, VQA_E_UNSUPPORTED,
+              "conv1d_transpose: supports stride 2, K 4, pad_left 1 (got s=%d K=%d p=%d)", stride, K, pad_left);
+  return VQA_OK;
+}
+
+static GatherArgs convT_fwd_gather(const void* x, const float* w, const float* bias, const void* residual, void* y,
+                                   int B, int T_in, int T_out, int C_in, int C_out, int K, int pad_left, int flags) {
+  return GatherArgs{x, w, bias, residual, nullptr, y, B, T_in, T_in, C_in, 2 * C_out, 3, 1, 1, 1,
+                    W_PAIR, K, pad_left, T_out, flags & (VQA_PRE_RELU | VQA_ADD_RESIDUAL | VQA_X_F32 | VQA_Y_F32)};
+}
+
+static GatherArgs convT_bwd_data_gather(const void* dy, const float* w, const void* mask, const void* residual,
+                                        void* dx, int B, int T_in, int T_out, int C_in, int C_out, int K, int stride,
+                                        int pad_left, int flags) {
+  return GatherArgs{dy, w, nullptr, residual, mask, dx, B, T_out, T_in, C_out, C_in, K, stride, 1, pad_left,
+                    W_DIRECT, K, 0, T_in, swap_xy_flags(flags)};
+}
+
+// flags the weight gradient of a conv keeps
+static int conv_wgrad_flags(int flags) { return flags & (VQA_PRE_RELU | VQA_X_F32 | VQA_Y_F32); }
+// flags of the gather weight-gradient a transposed conv's weight gradient runs (dy is its input)
+static int convT_wgrad_flags(int flags) { return (swap_xy_flags(flags) & (VQA_X_F32 | VQA_Y_F32)) | WG_DB_FROM_X; }
+
 extern "C" int vqa_conv1d_fwd(const void* x, const float* w, const float* bias, const void* residual, void* y, int B,
                               int T_in, int T_out, int C_in, int C_out, int K, int stride, int dilation, int pad_left,
                               int flags, int dtype, vqa_stream_t stream) {
@@ -2023,17 +2164,9 @@ extern "C" int vqa_conv1d_fwd(const void* x, const float* w, const float* bias, 
     return co1_fwd(x, w, bias, residual, y, B, T_in, C_in, K, dilation, pad_left,
                    flags & (VQA_PRE_RELU | VQA_ADD_RESIDUAL | VQA_X_F32 | VQA_Y_F32), dtype, (hipStream_t)stream);
   }
-  GatherArgs a{x, w, bias, residual, nullptr, y, B, T_in, T_out, C_in, C_out, K, stride, dilation, pad_left,
-               W_DIRECT, K, 0, T_out, flags & (VQA_PRE_RELU | VQA_ADD_RESIDUAL | VQA_X_F32 | VQA_Y_F32)};
+  const GatherArgs a = conv_fwd_gather(x, w, bias, residual, y, B, T_in, T_out, C_in, C_out, K, stride, dilation,
+                                       pad_left, flags);
   return run_gather(a, dtype, (hipStream_t)stream);
-}
-
-// flags for the data-gradient gather: the gather input is dy (y side), output dx (x side)
-static int swap_xy_flags(int flags) {
-  int f = flags & (VQA_POST_MASK | VQA_ADD_RESIDUAL);
-  if (flags & VQA_X_F32) f |= VQA_Y_F32;
-  if (flags & VQA_Y_F32) f |= VQA_X_F32;
-  return f;
 }
 
 extern "C" int vqa_conv1d_bwd_data(const void* dy, const float* w, const void* mask, const void* residual, void* dx,
@@ -2051,17 +2184,10 @@ extern "C" int vqa_conv1d_bwd_data(const void* dy, const float* w, const void* m
     return co1_bwd(dy, w, (flags & VQA_POST_MASK) ? mask : nullptr, residual, dx, B, T_in, C_in, K, dilation,
                    pad_left, f, dtype, nullptr, nullptr, (hipStream_t)stream);
   }
-  const int f = swap_xy_flags(flags);
-  if (stride == 1) {
-    GatherArgs a{dy, w, nullptr, residual, mask, dx, B, T_out, T_in, C_out, C_in, K, 1, dilation,
-                 (K - 1) * dilation - pad_left, W_FLIP_T, K, 0, T_in, f};
-    return run_gather(a, dtype, (hipStream_t)stream);
-  }
-  VQA_REQUIRE(stride == 2 && K == 4 && dilation == 1 && pad_left == 1, VQA_E_UNSUPPORTED,
-              "conv1d_bwd_data: strided data-gradient supports stride 2, K 4, pad_left 1 (got s=%d K=%d d=%d p=%d)",
-              stride, K, dilation, pad_left);
-  GatherArgs a{dy, w, nullptr, residual, mask, dx, B, T_out, T_out, C_out, 2 * C_in, 3, 1, 1, 1,
-               W_PAIR, K, pad_left, T_in, f};
+  GatherArgs a{};
+  const int rc = conv_bwd_data_gather(&a, dy, w, mask, residual, dx, B, T_in, T_out, C_in, C_out, K, stride, dilation,
+                                      pad_left, flags);
+  if (rc != VQA_OK) return rc;
   return run_gather(a, dtype, (hipStream_t)stream);
 }
 
@@ -2078,36 +2204,33 @@ extern "C" int vqa_conv1d_bwd_weight(const void* x, const void* dy, float* dw, f
           dilation, K);
   VQA_ARG(T_out == (T_in + stride - 1) / stride, "conv1d_bwd_weight: T_out %d != ceil(T_in/stride)", T_out);
   return run_wgrad(x, dy, dw, db, B, T_in, T_out, C_in, C_out, K, stride, dilation, pad_left,
-                   flags & (VQA_PRE_RELU | VQA_X_F32 | VQA_Y_F32), dtype, workspace, ws_bytes, (hipStream_t)stream,
+                   conv_wgrad_flags(flags), dtype, workspace, ws_bytes, (hipStream_t)stream,
                    nullptr);
 }
 
 extern "C" int vqa_conv1d_transpose_fwd(const void* x, const float* w, const float* bias, const void* residual,
                                         void* y, int B, int T_in, int T_out, int C_in, int C_out, int K, int stride,
                                         int pad_left, int flags, int dtype, vqa_stream_t stream) {
-  VQA_REQUIRE(stride == 2 && K == 4 && pad_left == 1, VQA_E_UNSUPPORTED,
-              "conv1d_transpose: supports stride 2, K 4, pad_left 1 (got s=%d K=%d p=%d)", stride, K, pad_left);
+  if (const int rc = convT_check(K, stride, pad_left)) return rc;
   VQA_ARG(T_out == stride * T_in, "conv1d_transpose_fwd: T_out %d != stride*T_in", T_out);
-  GatherArgs a{x, w, bias, residual, nullptr, y, B, T_in, T_in, C_in, 2 * C_out, 3, 1, 1, 1,
-               W_PAIR, K, pad_left, T_out, flags & (VQA_PRE_RELU | VQA_ADD_RESIDUAL | VQA_X_F32 | VQA_Y_F32)};
+  const GatherArgs a = convT_fwd_gather(x, w, bias, residual, y, B, T_in, T_out, C_in, C_out, K, pad_left, flags);
   return run_gather(a, dtype, (hipStream_t)stream);
 }
 
 extern "C" int vqa_conv1d_transpose_bwd_data(const void* dy, const float* w, const void* mask, const void* residual,
                                              void* dx, int B, int T_in, int T_out, int C_in, int C_out, int K,
                                              int stride, int pad_left, int flags, int dtype, vqa_stream_t stream) {
-  VQA_REQUIRE(stride == 2 && K == 4 && pad_left == 1, VQA_E_UNSUPPORTED,
-              "conv1d_transpose: supports stride 2, K 4, pad_left 1");
+  if (const int rc = convT_check(K, stride, pad_left)) return rc;
   VQA_ARG(T_out == stride * T_in, "conv1d_transpose_bwd_data: T_out %d != stride*T_in", T_out);
-  GatherArgs a{dy, w, nullptr, residual, mask, dx, B, T_out, T_in, C_out, C_in, K, stride, 1, pad_left,
-               W_DIRECT, K, 0, T_in, swap_xy_flags(flags)};
+  const GatherArgs a = convT_bwd_data_gather(dy, w, mask, residual, dx, B, T_in, T_out, C_in, C_out, K, stride,
+                                             pad_left, flags);
   return run_gather(a, dtype, (hipStream_t)stream);
 }
 
 extern "C" size_t vqa_conv1d_transpose_bwd_weight_workspace(int B, int T_in, int T_out, int C_in, int C_out, int K,
                                                             int stride, int pad_left, int flags, int dtype) {
   (void)pad_left;
-  const int f = (swap_xy_flags(flags) & (VQA_X_F32 | VQA_Y_F32)) | WG_DB_FROM_X;
+  const int f = convT_wgrad_flags(flags);
   return wgrad_ws(dtype, B, T_out, T_in, C_out, C_in, K, stride, 1, f);
 }
 
@@ -2115,12 +2238,11 @@ extern "C" int vqa_conv1d_transpose_bwd_weight(const void* x, const void* dy, fl
                                                int T_out, int C_in, int C_out, int K, int stride, int pad_left,
                                                int flags, int dtype, void* workspace, size_t ws_bytes,
                                                vqa_stream_t stream) {
-  VQA_REQUIRE(stride == 2 && K == 4 && pad_left == 1, VQA_E_UNSUPPORTED,
-              "conv1d_transpose: supports stride 2, K 4, pad_left 1");
+  if (const int rc = convT_check(K, stride, pad_left)) return rc;
   VQA_ARG(T_out == stride * T_in, "conv1d_transpose_bwd_weight: T_out %d != stride*T_in", T_out);
   // dW[k][co][ci] = sum_i dy[2i + k - 1][co] * x[i][ci]: the gather weight-gradient with dy as its input;
   // db[co] = column sums of dy, taken from the same staged rows (WG_DB_FROM_X)
-  const int f = (swap_xy_flags(flags) & (VQA_X_F32 | VQA_Y_F32)) | WG_DB_FROM_X;
+  const int f = convT_wgrad_flags(flags);
   return run_wgrad(dy, x, dw, db, B, T_out, T_in, C_out, C_in, K, stride, 1, pad_left, f, dtype, workspace, ws_bytes,
                    (hipStream_t)stream, nullptr);
 }
@@ -2134,7 +2256,7 @@ extern "C" int vqa_conv1d_bwd_weight_partials(const void* x, const void* dy, flo
           dilation, K);
   VQA_ARG(T_out == (T_in + stride - 1) / stride, "conv1d_bwd_weight: T_out %d != ceil(T_in/stride)", T_out);
   return run_wgrad(x, dy, dw, db, B, T_in, T_out, C_in, C_out, K, stride, dilation, pad_left,
-                   flags & (VQA_PRE_RELU | VQA_X_F32 | VQA_Y_F32), dtype, workspace, ws_bytes, (hipStream_t)stream,
+                   conv_wgrad_flags(flags), dtype, workspace, ws_bytes, (hipStream_t)stream,
                    desc);
 }
 
@@ -2144,10 +2266,9 @@ extern "C" int vqa_conv1d_transpose_bwd_weight_partials(const void* x, const voi
                                                         size_t ws_bytes, vqa_partials_desc* desc,
                                                         vqa_stream_t stream) {
   VQA_ARG(desc, "bwd_weight_partials: NULL descriptor");
-  VQA_REQUIRE(stride == 2 && K == 4 && pad_left == 1, VQA_E_UNSUPPORTED,
-              "conv1d_transpose: supports stride 2, K 4, pad_left 1");
+  if (const int rc = convT_check(K, stride, pad_left)) return rc;
   VQA_ARG(T_out == stride * T_in, "conv1d_transpose_bwd_weight: T_out %d != stride*T_in", T_out);
-  const int f = (swap_xy_flags(flags) & (VQA_X_F32 | VQA_Y_F32)) | WG_DB_FROM_X;
+  const int f = convT_wgrad_flags(flags);
   return run_wgrad(dy, x, dw, db, B, T_out, T_in, C_out, C_in, K, stride, 1, pad_left, f, dtype, workspace, ws_bytes,
                    (hipStream_t)stream, desc);
 }
@@ -2168,17 +2289,34 @@ static GatherArgs fused_bwd_args(const void* dy, const float* w, const void* x, 
   return a;
 }
 
-extern "C" size_t vqa_conv1d_bwd_data_weight_workspace(int B, int T_in, int T_out, int C_in, int C_out, int K,
-                                                       int stride, int dilation, int pad_left, int flags, int dtype) {
-  if (B < 1 || T_in < 1 || T_out < 1 || C_in < 1 || C_out < 1 || K < 1 || stride < 1 || dilation < 1) return 0;
-  size_t need = wgrad_ws(dtype, B, T_in, T_out, C_in, C_out, K, stride, dilation,
-                         flags & (VQA_PRE_RELU | VQA_X_F32 | VQA_Y_F32));
-  if (co1_supported(C_in, C_out, K, stride, dilation, dtype, flags)) need = std::max(need, co1_bwd_workspace(C_in, K));
+// how vqa_conv1d_bwd_data_weight runs: the one-output-channel kernel, the 32-channel kernel with the fused weight
+// gradient (*pvx = its x chunks per thread), or the data gradient followed by the weight gradient
+enum { F_CO1, F_CONV32, F_TWO_CALL };
+static int fused_route(int B, int T_in, int T_out, int C_in, int C_out, int K, int stride, int dilation, int pad_left,
+                       int flags, int dtype, int* pvx) {
+  *pvx = 0;
+  if (co1_supported(C_in, C_out, K, stride, dilation, dtype, flags)) return F_CO1;
   if (stride == 1) {
     const GatherArgs a = fused_bwd_args(nullptr, nullptr, nullptr, nullptr, nullptr, B, T_in, T_out, C_in, C_out, K,
                                         dilation, pad_left, flags);
-    if (conv32_pvx(a, dtype, true)) need = std::max(need, fused_bwd_ws(C_in, C_out, K));
+    if ((*pvx = conv32_pvx(a, dtype, true))) return F_CONV32;
   }
+  return F_TWO_CALL;
+}
+
+// the flags of the two calls of the fallback
+static int two_call_data_flags(int flags) {
+  return ((flags & VQA_PRE_RELU) ? VQA_POST_MASK : 0) | (flags & (VQA_ADD_RESIDUAL | VQA_X_F32 | VQA_Y_F32));
+}
+
+extern "C" size_t vqa_conv1d_bwd_data_weight_workspace(int B, int T_in, int T_out, int C_in, int C_out, int K,
+                                                       int stride, int dilation, int pad_left, int flags, int dtype) {
+  if (B < 1 || T_in < 1 || T_out < 1 || C_in < 1 || C_out < 1 || K < 1 || stride < 1 || dilation < 1) return 0;
+  size_t need = wgrad_ws(dtype, B, T_in, T_out, C_in, C_out, K, stride, dilation, conv_wgrad_flags(flags));
+  int pvx = 0;
+  const int route = fused_route(B, T_in, T_out, C_in, C_out, K, stride, dilation, pad_left, flags, dtype, &pvx);
+  if (route == F_CO1) need = std::max(need, co1_bwd_workspace(C_in, K));
+  if (route == F_CONV32) need = std::max(need, fused_bwd_ws(C_in, C_out, K));
   return need;
 }
 
@@ -2193,7 +2331,9 @@ extern "C" int vqa_conv1d_bwd_data_weight(const void* dy, const float* w, const 
   VQA_ARG(dy && w && x && dx && dw, "conv1d_bwd_data_weight: null tensor pointer");
   VQA_ARG(dtype == VQA_F32 || dtype == VQA_BF16, "unknown dtype %d", dtype);
   const hipStream_t s = (hipStream_t)stream;
-  if (co1_supported(C_in, C_out, K, stride, dilation, dtype, flags)) {
+  int pvx = 0;
+  const int route = fused_route(B, T_in, T_out, C_in, C_out, K, stride, dilation, pad_left, flags, dtype, &pvx);
+  if (route == F_CO1) {
     const size_t need = co1_bwd_workspace(C_in, K);
     VQA_ARG(workspace && ws_bytes >= need, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
     VQA_ARG(!(flags & VQA_ADD_RESIDUAL) || residual, "VQA_ADD_RESIDUAL without residual");
@@ -2212,36 +2352,158 @@ extern "C" int vqa_conv1d_bwd_data_weight(const void* dy, const float* w, const 
     VQA_LAUNCHED("reduce_partials_kernel");
     return VQA_OK;
   }
-  if (stride == 1) {
+  if (route == F_CONV32) {
     GatherArgs a = fused_bwd_args(dy, w, x, residual, dx, B, T_in, T_out, C_in, C_out, K, dilation, pad_left, flags);
-    if (const int pvx = conv32_pvx(a, dtype, true)) {
-      const size_t need = fused_bwd_ws(C_in, C_out, K);
-      VQA_ARG(workspace && ws_bytes >= need, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
-      a.wpart = (float*)workspace;
-      int nwg = 0;
-      const int rc = dtype == VQA_BF16 ? launch_conv32<bf16, true>(a, pvx, s, &nwg)
-                                       : launch_conv32<float, true>(a, pvx, s, &nwg);
-      if (rc != VQA_OK) return rc;
-      const int KCO = K * C_in * C_out, E = KCO + C_out;
-      if (desc) {
-        *desc = vqa_partials_desc{(const float*)workspace, dw, db, nwg, E, KCO, 0};
-        return VQA_OK;
-      }
-      hipLaunchKernelGGL(reduce_partials_kernel, dim3((E + kRedCols - 1) / kRedCols), dim3(256), 0, s, (const float*)workspace, nwg, E,
-                         KCO, dw, db);
-      VQA_LAUNCHED("reduce_partials_kernel");
+    const size_t need = fused_bwd_ws(C_in, C_out, K);
+    VQA_ARG(workspace && ws_bytes >= need, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
+    a.wpart = (float*)workspace;
+    int nwg = 0;
+    const int rc = dtype == VQA_BF16 ? launch_conv32<bf16, true>(a, pvx, s, &nwg)
+                                     : launch_conv32<float, true>(a, pvx, s, &nwg);
+    if (rc != VQA_OK) return rc;
+    const int KCO = K * C_in * C_out, E = KCO + C_out;
+    if (desc) {
+      *desc = vqa_partials_desc{(const float*)workspace, dw, db, nwg, E, KCO, 0};
       return VQA_OK;
     }
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((E + kRedCols - 1) / kRedCols), dim3(256), 0, s, (const float*)workspace, nwg, E,
+                       KCO, dw, db);
+    VQA_LAUNCHED("reduce_partials_kernel");
+    return VQA_OK;
   }
-  // not fusable here: data gradient, then the weight gradient from the same operands
+  // not fusable here: data gradient, then the weight gradient from the same operands. A weight gradient the
+  // library cannot serve is refused before the data gradient is launched.
+  WgradPlan wp{};
+  int rc = wgrad_route(&wp, dtype, B, T_in, T_out, C_in, C_out, K, stride, dilation, conv_wgrad_flags(flags));
+  if (rc != VQA_OK) return rc;
   const bool relu = flags & VQA_PRE_RELU;
-  int rc = vqa_conv1d_bwd_data(dy, w, relu ? x : nullptr, residual, dx, B, T_in, T_out, C_in, C_out, K, stride,
-                               dilation, pad_left,
-                               (relu ? VQA_POST_MASK : 0) | (flags & (VQA_ADD_RESIDUAL | VQA_X_F32 | VQA_Y_F32)),
-                               dtype, stream);
+  rc = vqa_conv1d_bwd_data(dy, w, relu ? x : nullptr, residual, dx, B, T_in, T_out, C_in, C_out, K, stride, dilation,
+                           pad_left, two_call_data_flags(flags), dtype, stream);
   if (rc != VQA_OK) return rc;
   return run_wgrad(x, dy, dw, db, B, T_in, T_out, C_in, C_out, K, stride, dilation, pad_left,
-                   flags & (VQA_PRE_RELU | VQA_X_F32 | VQA_Y_F32), dtype, workspace, ws_bytes, s, desc);
+                   conv_wgrad_flags(flags), dtype, workspace, ws_bytes, s, desc);
+}
+
+// ---- which kernel a conv call runs (host only)
+static void gather_detail(const GatherArgs& a, int dtype, int* family, int* d) {
+  const GatherRoute r = gather_route(a, dtype);
+  switch (r.family) {
+    case G_CONV32:
+      *family = VQA_ROUTE_CONV32;
+      d[0] = a.O, d[1] = r.pvx, d[2] = gather_nep(a, false), d[3] = 0;
+      break;
+    case G_MFMA:
+      *family = VQA_ROUTE_GATHER_MFMA;
+      d[0] = a.C, d[1] = a.O, d[2] = r.m.pv, d[3] = r.m.tm, d[4] = r.m.nep;
+      break;
+    case G_CI1: *family = VQA_ROUTE_CI1, d[0] = a.O, d[1] = a.K == 4 ? 4 : 0; break;
+    case G_THINO: *family = VQA_ROUTE_THIN_O, d[0] = a.C; break;
+    case G_THIN: *family = VQA_ROUTE_THIN, d[0] = a.O % 8 == 0 ? 8 : 1; break;
+    default: *family = VQA_ROUTE_DIRECT; d[0] = a.C, d[1] = a.O; break;
+  }
+}
+
+static int gather_route_rc(const GatherArgs& a, int dtype, int* family, int* d) {
+  const int rc = gather_check(a, dtype);
+  if (rc != VQA_OK) return rc;
+  gather_detail(a, dtype, family, d);
+  VQA_REQUIRE(*family != VQA_ROUTE_THIN || gather_thin_fits(a), VQA_E_UNSUPPORTED, "thin conv: tensor too large");
+  return VQA_OK;
+}
+
+static int wgrad_route_rc(int dtype, int B, int T_in, int T_out, int C, int O, int K, int S, int D, int flags,
+                          int* family, int* d) {
+  WgradPlan p{};
+  const int rc = wgrad_route(&p, dtype, B, T_in, T_out, C, O, K, S, D, flags);
+  if (rc != VQA_OK) return rc;
+  *family = p.kind == WG_MFMA ? VQA_ROUTE_WGRAD_MFMA : (p.kind == WG_DIRECT ? VQA_ROUTE_WGRAD_DIRECT : VQA_ROUTE_WGRAD_THIN);
+  d[0] = C, d[1] = O, d[2] = p.TT;
+  if (p.kind == WG_THIN_X || p.kind == WG_THIN_G) d[2] = p.kind == WG_THIN_X ? 1 : 0;
+  return VQA_OK;
+}
+
+extern "C" int vqa_conv1d_route(int op, int B, int T_in, int T_out, int C_in, int C_out, int K, int stride,
+                                int dilation, int pad_left, int flags, int dtype, int* detail) {
+  int d[VQA_ROUTE_DETAIL] = {0}, family = -1, rc = VQA_OK;
+  VQA_ARG(dtype == VQA_F32 || dtype == VQA_BF16, "unknown dtype %d", dtype);
+  VQA_ARG(stride >= 1 && dilation >= 1 && K >= 1, "conv1d_route: stride %d, dilation %d, K %d must be >= 1", stride,
+          dilation, K);
+  const bool transposed = op == VQA_OP_T_FWD || op == VQA_OP_T_BWD_DATA || op == VQA_OP_T_BWD_WEIGHT;
+  if (transposed) {
+    if ((rc = convT_check(K, stride, pad_left))) return rc;
+    VQA_ARG(T_out == stride * T_in, "conv1d_route: T_out %d != stride*T_in", T_out);
+  } else {
+    VQA_ARG(T_out == (T_in + stride - 1) / stride, "conv1d_route: T_out %d != ceil(T_in/stride)", T_out);
+  }
+  const bool co1 = !transposed && co1_supported(C_in, C_out, K, stride, dilation, dtype, flags);
+  switch (op) {
+    case VQA_OP_FWD:
+      if (co1) {
+        family = VQA_ROUTE_CO1, d[0] = C_in;
+      } else {
+        rc = gather_route_rc(conv_fwd_gather(nullptr, nullptr, nullptr, nullptr, nullptr, B, T_in, T_out, C_in, C_out,
+                                             K, stride, dilation, pad_left, flags),
+                             dtype, &family, d);
+      }
+      break;
+    case VQA_OP_BWD_DATA:
+      if (co1) {
+        family = VQA_ROUTE_CO1, d[0] = C_in;
+      } else {
+        GatherArgs a{};
+        rc = conv_bwd_data_gather(&a, nullptr, nullptr, nullptr, nullptr, nullptr, B, T_in, T_out, C_in, C_out, K,
+                                  stride, dilation, pad_left, flags);
+        if (rc == VQA_OK) rc = gather_route_rc(a, dtype, &family, d);
+      }
+      break;
+    case VQA_OP_BWD_WEIGHT:
+      rc = wgrad_route_rc(dtype, B, T_in, T_out, C_in, C_out, K, stride, dilation, conv_wgrad_flags(flags),
+                          &family, d);
+      break;
+    case VQA_OP_BWD_DATA_WEIGHT: {
+      VQA_ARG(B > 0 && T_in > 0 && C_in > 0 && C_out > 0, "non-positive shape");
+      int pvx = 0;
+      const int route = fused_route(B, T_in, T_out, C_in, C_out, K, stride, dilation, pad_left, flags, dtype, &pvx);
+      if (route == F_CO1) {
+        family = VQA_ROUTE_CO1, d[0] = C_in;
+      } else if (route == F_CONV32) {
+        const GatherArgs a = fused_bwd_args(nullptr, nullptr, nullptr, nullptr, nullptr, B, T_in, T_out, C_in, C_out,
+                                            K, dilation, pad_left, flags);
+        family = VQA_ROUTE_CONV32;
+        d[0] = a.O, d[1] = pvx, d[2] = gather_nep(a, true), d[3] = 1;
+      } else {
+        // detail: the families of the two calls; their own details come from a query of each op
+        int scratch[VQA_ROUTE_DETAIL] = {0};
+        rc = wgrad_route_rc(dtype, B, T_in, T_out, C_in, C_out, K, stride, dilation, conv_wgrad_flags(flags), &d[1],
+                            scratch);
+        if (rc != VQA_OK) return rc;
+        const int data = vqa_conv1d_route(VQA_OP_BWD_DATA, B, T_in, T_out, C_in, C_out, K, stride, dilation, pad_left,
+                                          two_call_data_flags(flags), dtype, scratch);
+        if (data < 0) return data;
+        d[0] = data;
+        family = VQA_ROUTE_TWO_CALL;
+      }
+      break;
+    }
+    case VQA_OP_T_FWD:
+      rc = gather_route_rc(convT_fwd_gather(nullptr, nullptr, nullptr, nullptr, nullptr, B, T_in, T_out, C_in, C_out, K,
+                                            pad_left, flags),
+                           dtype, &family, d);
+      break;
+    case VQA_OP_T_BWD_DATA:
+      rc = gather_route_rc(convT_bwd_data_gather(nullptr, nullptr, nullptr, nullptr, nullptr, B, T_in, T_out, C_in,
+                                                 C_out, K, stride, pad_left, flags),
+                           dtype, &family, d);
+      break;
+    case VQA_OP_T_BWD_WEIGHT:
+      rc = wgrad_route_rc(dtype, B, T_out, T_in, C_out, C_in, K, stride, 1, convT_wgrad_flags(flags), &family, d);
+      break;
+    default: vqa::set_error("conv1d_route: unknown op %d", op); return VQA_E_INVALID_ARG;
+  }
+  if (rc != VQA_OK) return rc;
+  if (detail)
+    for (int i = 0; i < VQA_ROUTE_DETAIL; ++i) detail[i] = d[i];
+  return family;
 }
 
 extern "C" int vqa_reduce_partials(const vqa_partials_desc* descs, int count, vqa_stream_t stream) {

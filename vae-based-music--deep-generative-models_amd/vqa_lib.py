@@ -30,7 +30,7 @@ EXPORTED = [
     "vqa_vq_reset_rows", "vqa_vq_ema_apply", "vqa_vq_ema_apply_derived", "vqa_reset_perm_index",
     "vqa_mse_loss", "vqa_mse_loss_workspace", "vqa_adam_keras", "vqa_lr_schedule", "vqa_counter_add",
     "vqa_conv1d_bwd_weight_partials", "vqa_conv1d_transpose_bwd_weight_partials", "vqa_reduce_partials",
-    "vqa_conv1d_bwd_data_weight", "vqa_conv1d_bwd_data_weight_workspace",
+    "vqa_conv1d_bwd_data_weight", "vqa_conv1d_bwd_data_weight_workspace", "vqa_conv1d_route",
     "vqa_spectral_loss", "vqa_spectral_loss_workspace", "vqa_stft_magnitude",
     "vqa_vq_argmin_split", "vqa_vq_split_bf16x3",
     "vqa_resblock_supported", "vqa_resblock_fwd", "vqa_resblock_bwd", "vqa_resblock_bwd_workspace",
@@ -103,6 +103,7 @@ _SIGS = {
     "vqa_reduce_partials": (_I, [_P, _I, _P]),
     "vqa_conv1d_bwd_data_weight": (_I, [_P, _P, _P, _P, _P, _P, _P] + _CONV + [_P, _S, _P, _P]),
     "vqa_conv1d_bwd_data_weight_workspace": (_S, _CONV),
+    "vqa_conv1d_route": (_I, [_I] + _CONV + [_P]),
     "vqa_spectral_loss": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _S, _P]),
     "vqa_spectral_loss_workspace": (_S, [_I, _I, _P, _P, _P, _I, _I]),
     "vqa_stft_magnitude": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
@@ -226,6 +227,33 @@ def same_out_len(T_in: int, stride: int) -> int:
 
 def reset_perm_index(seed: int, counter: int, level: int, M: int, k: int) -> int:
     return lib().vqa_reset_perm_index(seed, counter, level, M, k)
+
+
+# which kernel a conv call runs (vqa_conv1d_route): ops, kernel families, and the names of the detail entries
+OP_FWD, OP_BWD_DATA, OP_BWD_WEIGHT, OP_BWD_DATA_WEIGHT, OP_T_FWD, OP_T_BWD_DATA, OP_T_BWD_WEIGHT = range(7)
+ROUTE_FAMILIES = ("co1", "conv32", "gather_mfma", "ci1", "thinO", "thin", "direct", "wgrad_mfma", "wgrad_thin",
+                  "wgrad_direct", "two_call")
+_ROUTE_DETAIL = {
+    "co1": ("C",), "conv32": ("O", "PVX", "NEP", "FW"), "gather_mfma": ("C", "O", "PV", "TM", "NEP"),
+    "ci1": ("O", "KT"), "thinO": ("C",), "thin": ("OV",), "direct": ("C", "O"), "wgrad_mfma": ("C", "O", "TT"),
+    "wgrad_thin": ("C", "O", "wide_x"), "wgrad_direct": ("C", "O", "TT"), "two_call": ("data", "weight"),
+}
+ROUTE_DETAIL = 8
+
+
+def conv1d_route(op, B, T_in, T_out, C_in, C_out, K, stride, dilation, pad, flags, dtype):
+    """(family, detail) of the kernel the conv call `op` with these arguments runs: the family's name and a dict of
+    its template parameters (for "two_call" the families of its two calls). Host-only: needs no GPU. Raises
+    VQAError where the call itself would be refused."""
+    d = (ctypes.c_int * ROUTE_DETAIL)()
+    rc = lib().vqa_conv1d_route(op, B, T_in, T_out, C_in, C_out, K, stride, dilation, pad, flags, dtype, d)
+    if rc < 0:
+        _check(rc, "vqa_conv1d_route")
+    fam = ROUTE_FAMILIES[rc]
+    det = dict(zip(_ROUTE_DETAIL[fam], list(d)))
+    if fam == "two_call":
+        det = {k: ROUTE_FAMILIES[v] for k, v in det.items()}
+    return fam, det
 
 
 # ---- device ops ------------------------------------------------------------------------------------
