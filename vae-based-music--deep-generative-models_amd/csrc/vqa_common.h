@@ -44,6 +44,30 @@ template <> __device__ __forceinline__ void st4<bf16>(bf16* p, f32x4 v) {
   *(bf16x4*)p = o;
 }
 
+// 8 consecutive elements <-> 8 floats (16 B for bf16, 2 x 16 B for f32; caller guarantees 16-byte alignment)
+template <class T> __device__ __forceinline__ void ld8(const T* p, float* v);
+template <> __device__ __forceinline__ void ld8<bf16>(const bf16* p, float* v) {
+  const bf16x8 x = *(const bf16x8*)p;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (float)x[j];
+}
+template <> __device__ __forceinline__ void ld8<float>(const float* p, float* v) {
+  const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[j] = a[j];
+    v[j + 4] = b[j];
+  }
+}
+template <class T> __device__ __forceinline__ void st8(T* p, const float* v);
+template <> __device__ __forceinline__ void st8<bf16>(bf16* p, const float* v) {
+  *(bf16x8*)p = bf16x8{(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3], (bf16)v[4], (bf16)v[5], (bf16)v[6], (bf16)v[7]};
+}
+template <> __device__ __forceinline__ void st8<float>(float* p, const float* v) {
+  *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
+  *(f32x4*)(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
+}
+
 // ---- cross-lane moves on the VALU (DPP, v_permlane*_swap, v_readlane) ------------------------------------
 // The library's reductions and lane exchanges use these instead of __shfl* (ds_bpermute_b32 through the LDS
 // crossbar): no LDS instruction, no LDS allocation needed, and — where the values are summed — a fixed pairing

@@ -122,28 +122,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* x, const T*
 template <int R>
 __device__ __forceinline__ float grp_sum_r(float v) { return xl::grp_sum<R>(v); }
 
-template <class T> __device__ __forceinline__ void ld8v(const T* p, float (&v)[8]);
-template <> __device__ __forceinline__ void ld8v<bf16>(const bf16* p, float (&v)[8]) {
-  const bf16x8 b = *(const bf16x8*)p;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = (float)b[i];
-}
-template <> __device__ __forceinline__ void ld8v<float>(const float* p, float (&v)[8]) {
-  const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-  v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
-}
-template <class T> __device__ __forceinline__ void st8v(T* p, const float (&v)[8]);
-template <> __device__ __forceinline__ void st8v<bf16>(bf16* p, const float (&v)[8]) {
-  bf16x8 b;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) b[i] = (bf16)v[i];
-  *(bf16x8*)p = b;
-}
-template <> __device__ __forceinline__ void st8v<float>(float* p, const float (&v)[8]) {
-  *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
-  *(f32x4*)(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-}
-
 template <class T, int R>
 __global__ __launch_bounds__(256) void layernorm8_fwd_kernel(const T* x, const float* gamma, const float* beta, T* y,
                                                             long long rows, float eps) {
@@ -155,7 +133,7 @@ __global__ __launch_bounds__(256) void layernorm8_fwd_kernel(const T* x, const f
   const long long rstep = (long long)gridDim.x * 4 * RPW;
   for (long long r = ((long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * RPW + sub; r < rows; r += rstep) {
     float v[8];
-    ld8v(x + r * C + c0, v);
+    ld8(x + r * C + c0, v);
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) s += v[i];
@@ -166,7 +144,7 @@ __global__ __launch_bounds__(256) void layernorm8_fwd_kernel(const T* x, const f
     const float inv = 1.0f / sqrtf(grp_sum_r<R>(q) / (float)C + eps);
 #pragma unroll
     for (int i = 0; i < 8; ++i) v[i] = (v[i] - mean) * inv * gm[i] + bt[i];
-    st8v(y + r * C + c0, v);
+    st8(y + r * C + c0, v);
   }
 }
 
@@ -183,8 +161,8 @@ __global__ __launch_bounds__(256) void layernorm8_bwd_kernel(const T* x, const T
   const long long r0 = (long long)blockIdx.x * rows_per_wg, r1 = std::min(rows, r0 + rows_per_wg);
   for (long long r = r0 + wave * RPW + sub; r < r1; r += 4 * RPW) {
     float v[8], d[8];
-    ld8v(x + r * C + c0, v);
-    ld8v(dy + r * C + c0, d);
+    ld8(x + r * C + c0, v);
+    ld8(dy + r * C + c0, d);
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) s += v[i];
@@ -206,7 +184,7 @@ __global__ __launch_bounds__(256) void layernorm8_bwd_kernel(const T* x, const T
     const float mg = grp_sum_r<R>(sg) / (float)C, mgx = grp_sum_r<R>(sgx) / (float)C;
 #pragma unroll
     for (int i = 0; i < 8; ++i) g[i] = inv * ((g[i] - mg) - v[i] * mgx);
-    st8v(dx + r * C + c0, g);
+    st8(dx + r * C + c0, g);
   }
   // combine the wave's row groups (lanes with the same channels: xor R, 2R, ...), then the 4 waves in order
 #pragma unroll

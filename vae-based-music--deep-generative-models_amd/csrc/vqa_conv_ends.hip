@@ -8,7 +8,7 @@
 // through LDS. The backward reads x once and writes dx once, computing the weight gradient from the same
 // registers: dx[r][c] = sum_k dy[r - k*D + P] w[k][c], dW[k][c] += act(x[r][c]) dy[r - k*D + P]
 // (per-workgroup fp32 partials, reduced in a fixed order by vqa_reduce_partials: deterministic).
-#include "vqa_common.h"
+#include "vqa_launch.h"
 
 namespace vqa {
 
@@ -202,15 +202,6 @@ __global__ __launch_bounds__(256) void co1_bwd_kernel(Co1Args a) {
   if (threadIdx.x == 0) out[a.K * C] = db;
 }
 
-static int co1_cus() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    return v;
-  }();
-  return n;
-}
 constexpr int kCo1PerCU = 4;
 
 bool co1_supported(int C, int O, int K, int S, int D, int dtype, int flags) {
@@ -220,7 +211,7 @@ bool co1_supported(int C, int O, int K, int S, int D, int dtype, int flags) {
   return (K - 1) * D <= rpp && (K - 1) * D <= 3 * 64;
 }
 
-size_t co1_bwd_workspace(int C, int K) { return (size_t)co1_cus() * kCo1PerCU * (K * C + 1) * sizeof(float); }
+size_t co1_bwd_workspace(int C, int K) { return (size_t)cu_count() * kCo1PerCU * (K * C + 1) * sizeof(float); }
 
 template <class TX, class TY, int C>
 static int co1_fwd_launch(const Co1Args& a, hipStream_t s) {
@@ -249,12 +240,11 @@ int co1_fwd(const void* x, const float* w, const float* bias, const void* resid,
   a.ntb = (T + kCo1TB - 1) / kCo1TB;
   const bool xf = dtype == VQA_F32 || (flags & VQA_X_F32);
   const bool yf = dtype == VQA_F32 || (flags & VQA_Y_F32);
-  if (C == 64) {
-    if (xf) return yf ? co1_fwd_launch<float, float, 64>(a, s) : co1_fwd_launch<float, bf16, 64>(a, s);
-    return yf ? co1_fwd_launch<bf16, float, 64>(a, s) : co1_fwd_launch<bf16, bf16, 64>(a, s);
-  }
-  if (xf) return yf ? co1_fwd_launch<float, float, 32>(a, s) : co1_fwd_launch<float, bf16, 32>(a, s);
-  return yf ? co1_fwd_launch<bf16, float, 32>(a, s) : co1_fwd_launch<bf16, bf16, 32>(a, s);
+  return dispatch_xy(xf, yf, [&](auto tx, auto ty) {
+    typedef tag_t<decltype(tx)> TX;
+    typedef tag_t<decltype(ty)> TY;
+    return C == 64 ? co1_fwd_launch<TX, TY, 64>(a, s) : co1_fwd_launch<TX, TY, 32>(a, s);
+  });
 }
 
 // ws == NULL: data gradient only (x = the ReLU' mask or NULL). Else also the weight-gradient partials;
@@ -264,18 +254,17 @@ int co1_bwd(const void* dy, const float* w, const void* x, const void* resid, vo
   Co1Args a{x, w, nullptr, resid, nullptr, dy, dx, (float*)ws, B, T, K, D, P, flags, 0, 0, 0};
   a.ntb = (T + kCo1TB - 1) / kCo1TB;
   a.ntiles = a.ntb * B;
-  int nwg = co1_cus() * kCo1PerCU;
+  int nwg = cu_count() * kCo1PerCU;
   if (nwg > a.ntiles) nwg = a.ntiles;
   a.tpw = (a.ntiles + nwg - 1) / nwg;
   if (nparts) *nparts = (a.ntiles + a.tpw - 1) / a.tpw;
   const bool xf = dtype == VQA_F32 || (flags & VQA_X_F32);
   const bool gf = dtype == VQA_F32 || (flags & VQA_Y_F32);
-  if (C == 64) {
-    if (xf) return gf ? co1_bwd_launch<float, float, 64>(a, s) : co1_bwd_launch<float, bf16, 64>(a, s);
-    return gf ? co1_bwd_launch<bf16, float, 64>(a, s) : co1_bwd_launch<bf16, bf16, 64>(a, s);
-  }
-  if (xf) return gf ? co1_bwd_launch<float, float, 32>(a, s) : co1_bwd_launch<float, bf16, 32>(a, s);
-  return gf ? co1_bwd_launch<bf16, float, 32>(a, s) : co1_bwd_launch<bf16, bf16, 32>(a, s);
+  return dispatch_xy(xf, gf, [&](auto tx, auto tg) {
+    typedef tag_t<decltype(tx)> TX;
+    typedef tag_t<decltype(tg)> TG;
+    return C == 64 ? co1_bwd_launch<TX, TG, 64>(a, s) : co1_bwd_launch<TX, TG, 32>(a, s);
+  });
 }
 
 }  // namespace vqa

@@ -12,23 +12,13 @@
 //   src/autoregressive/autoregressive_fmha.py:162-240    sample (Gumbel-max per step)      -> vqa_prior_decode
 // Activations are channels-last (rows = N*T, C) in the compute dtype; weights fp32 (Keras layouts); every
 // reduction runs in a fixed order (weight gradients as per-workgroup partial rows for vqa_reduce_partials).
-#include "vqa_common.h"
+#include "vqa_launch.h"
 #include "vqa_mfma.h"
 #include <algorithm>
 #include <math.h>
 #include <type_traits>
 
 namespace vqa {
-
-static int pr_cus() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    return v;
-  }();
-  return n;
-}
 
 // counter-based uniform in (0, 1): splitmix64 chain over (seed, a, b, c), 24 high bits (oracle/prior_ref.py
 // gumbel_uniform restates it)
@@ -1896,15 +1886,6 @@ static size_t seqlin_lds(int K, int N, int taps, int esz) {
 static size_t wgrad_lds(int K, int N, int taps, int esz) {
   return ((size_t)(64 + taps - 1) * (K + 16 / esz) + (size_t)64 * (N + 16 / esz)) * esz;
 }
-static int set_lds_attr(const void* fn, size_t bytes) {
-  if (bytes <= 65536) return VQA_OK;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("prior: cannot reserve %zu B of LDS", bytes);
-    return VQA_E_UNSUPPORTED;
-  }
-  return VQA_OK;
-}
 
 template <class T>
 static int launch_seqlin(const SeqLinArgs& a, hipStream_t s) {
@@ -1929,12 +1910,12 @@ static int launch_seqlin(const SeqLinArgs& a, hipStream_t s) {
     const bool chunks = a.taps != 1 || (a.ldy % vec == 0 && ((uintptr_t)a.y & 15) == 0 &&
                                         (!a.r || (a.ldr % vec == 0 && ((uintptr_t)a.r & 15) == 0)));
     if (fn && chunks && lds <= 160 * 1024) {
-      if (int rc = set_lds_attr(fn, lds)) return rc;
+      if (int rc = raise_dyn_lds(fn, lds, "prior")) return rc;
       SeqLinArgs c = a;
       c.tiles_per_seq = (a.T + 16 * waves - 1) / (16 * waves);
       int ntiles = a.nseq * c.tiles_per_seq;
       const int per_cu = std::max(1, std::min<int>(max_per_cu, (int)(160 * 1024 / lds)));
-      const int nwg = std::min(ntiles, pr_cus() * per_cu);
+      const int nwg = std::min(ntiles, cu_count() * per_cu);
       void* args[] = {&c, &ntiles};
       (void)hipLaunchKernel(fn, dim3(nwg), dim3(64 * waves), args, lds, s);
       VQA_LAUNCHED("seqlin_d_kernel");
@@ -1946,7 +1927,7 @@ static int launch_seqlin(const SeqLinArgs& a, hipStream_t s) {
               a.taps);
   const void* fn = a.N <= 32 ? (const void*)seqlin_kernel<T, 2> : (const void*)seqlin_kernel<T, 8>;
   const size_t lds = seqlin_lds(a.K, a.N, a.taps, sizeof(T));
-  if (int rc = set_lds_attr(fn, lds)) return rc;
+  if (int rc = raise_dyn_lds(fn, lds, "prior")) return rc;
   SeqLinArgs c = a;
   void* args[] = {&c};
   (void)hipLaunchKernel(fn, dim3(a.nseq * a.tiles_per_seq), dim3(256), args, lds, s);
@@ -1964,7 +1945,7 @@ static const void* wgrad_fn(int ppw, int N) {
 
 static void wgrad_plan(int nseq, int T, int& seg_rows, int& segs) {
   // about 2 workgroups per CU in total, segments a multiple of the 64-row chunk
-  const long long target = std::max<long long>(1, (long long)2 * pr_cus() / std::max(1, nseq));
+  const long long target = std::max<long long>(1, (long long)2 * cu_count() / std::max(1, nseq));
   seg_rows = (int)std::max<long long>(64, ((T + target - 1) / target + 63) / 64 * 64);
   segs = (T + seg_rows - 1) / seg_rows;
 }
@@ -2065,7 +2046,7 @@ extern "C" int vqa_seqlin_wgrad(const void* x, int64_t ldx, const void* dy, int6
   const int ppw = (taps * K / 16 + 3) / 4;
   const void* fn = dtype == VQA_BF16 ? wgrad_fn<bf16>(ppw, N) : wgrad_fn<float>(ppw, N);
   const size_t lds = wgrad_lds(K, N, taps, esz);
-  if (int rc = set_lds_attr(fn, lds)) return rc;
+  if (int rc = raise_dyn_lds(fn, lds, "prior")) return rc;
   void* args[] = {&a};
   (void)hipLaunchKernel(fn, dim3(nseq * segs), dim3(256), args, lds, (hipStream_t)stream);
   VQA_LAUNCHED("seqlin_wgrad_kernel");
@@ -2230,7 +2211,7 @@ template <class T>
 static int launch_head(int which, const HeadArgs& a, unsigned grid, size_t lds, hipStream_t s) {
   const void* fn = which == 0 ? (const void*)head_fwd_kernel<T>
                               : which == 1 ? (const void*)head_bwd_dx_kernel<T> : (const void*)head_bwd_dw_kernel<T>;
-  if (int rc = set_lds_attr(fn, lds)) return rc;
+  if (int rc = raise_dyn_lds(fn, lds, "prior")) return rc;
   HeadArgs c = a;
   void* args[] = {&c};
   (void)hipLaunchKernel(fn, dim3(grid), dim3(256), args, lds, s);
@@ -2253,7 +2234,7 @@ extern "C" int vqa_head_fwd(const void* x, const void* wt, const float* bias, co
 
 static int head_segs(int64_t M, int V) {
   const int nvt = (V + 63) / 64;
-  const long long want = std::max<long long>(1, (long long)2 * pr_cus() / nvt);
+  const long long want = std::max<long long>(1, (long long)2 * cu_count() / nvt);
   return (int)std::min<long long>(want, (M + 63) / 64);
 }
 

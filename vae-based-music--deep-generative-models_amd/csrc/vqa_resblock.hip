@@ -17,7 +17,7 @@
 // the weight gradients accumulate in registers across the persistent workgroup's tiles and leave as one
 // fp32 partial row per workgroup (reduced in a fixed order by vqa_reduce_partials: deterministic).
 // All products are MFMA (bf16 16x16x32 or the exact fp32 16x16x4 in parity mode), fp32 accumulation.
-#include "vqa_common.h"
+#include "vqa_launch.h"
 #include "vqa_mfma.h"
 #include <algorithm>
 #include <type_traits>
@@ -899,15 +899,6 @@ __global__ __launch_bounds__(256 * HALVES) void resblock_bwd_kernel(ResArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-static int rs_cus() {
-  static int n = [] {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    return v;
-  }();
-  return n;
-}
 constexpr int kResPerCU = 2;  // persistent workgroups per CU (also bounds the partial rows)
 // backward: tiles per workgroup at least (bounds the partial rows of short launches). 2 against 4, 3 and 1 in
 // alternating same-box runs: 7.316 ms/step (5 runs) vs 7.363 (4), 7.355 (3), 7.369 (1): level 2's short launches
@@ -923,24 +914,6 @@ static size_t fwd_lds(int d, int esz, int rt) {
 static size_t bwd_lds(int d, int esz, int rt) {
   const int s = RC + 16 / esz, HR = round16(rt + 2 * d);
   return ((size_t)(HR + 2 * d) * s + (size_t)(HR + 2) * s + (size_t)2 * HR * s + s) * esz;
-}
-
-static int set_lds(const void* fn, size_t bytes) {
-  constexpr int NS = 32;
-  static size_t done[NS] = {};
-  static const void* fns[NS] = {};
-  if (bytes <= 65536) return VQA_OK;
-  int slot = 0;
-  while (slot < NS - 1 && fns[slot] && fns[slot] != fn) ++slot;
-  if (fns[slot] == fn && done[slot] >= bytes) return VQA_OK;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("resblock: cannot reserve %zu B of LDS", bytes);
-    return VQA_E_UNSUPPORTED;
-  }
-  fns[slot] = fn;
-  done[slot] = bytes;
-  return VQA_OK;
 }
 
 // kernel instance for a dilation: the model's dilations (3^i, i < 4) are compiled constants
@@ -980,7 +953,7 @@ static void plan(ResArgs& a, int per_cu, int rt, int min_tiles = 1) {
   a.ntiles = a.ntm * a.B;
   // every slot gets floor(ntiles / nwg) tiles and the first (ntiles mod nwg) one more: workgroups w and
   // w + #CUs (dispatched to the same CU) never both hold an extra tile while extras <= #CUs
-  a.nwg = std::min(rs_cus() * per_cu, std::max(1, a.ntiles / min_tiles));
+  a.nwg = std::min(cu_count() * per_cu, std::max(1, a.ntiles / min_tiles));
   a.tpw = a.ntiles / a.nwg;
   a.textra = a.ntiles - a.tpw * a.nwg;
 }
@@ -1018,7 +991,7 @@ extern "C" int vqa_resblock_fwd(const void* x, const float* wa, const float* ba,
   const hipStream_t s = (hipStream_t)stream;
   const dim3 grid(a.nwg);
   const void* fn = dtype == VQA_BF16 ? rs_pick<RsFwd<bf16>>(dilation) : rs_pick<RsFwd<float>>(dilation);
-  if (int rc = set_lds(fn, lds)) return rc;
+  if (int rc = raise_dyn_lds(fn, lds, "resblock_fwd_kernel")) return rc;
   void* args[] = {&a};
   (void)hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
   VQA_LAUNCHED("resblock_fwd_kernel");
@@ -1031,7 +1004,7 @@ extern "C" size_t vqa_resblock_bwd_workspace(int B, int T, int C, int dilation, 
   (void)T;
   (void)dilation;
   (void)dtype;
-  return (size_t)2 * rs_cus() * kResPerCU * (3 * C * C + C) * sizeof(float);
+  return (size_t)2 * cu_count() * kResPerCU * (3 * C * C + C) * sizeof(float);
 }
 
 extern "C" int vqa_resblock_bwd(const void* dy, const void* x, const float* wa, const float* ba, const float* wb,
@@ -1060,7 +1033,7 @@ extern "C" int vqa_resblock_bwd(const void* dy, const void* x, const float* wa, 
   const void* fn = rt != bwd_rt_of(dilation)
                        ? (dtype == VQA_BF16 ? rs_pick<RsBwd128<bf16>>(dilation) : rs_pick<RsBwd128<float>>(dilation))
                        : (dtype == VQA_BF16 ? rs_pick<RsBwd<bf16>>(dilation) : rs_pick<RsBwd<float>>(dilation));
-  if (int rc = set_lds(fn, lds_max)) return rc;
+  if (int rc = raise_dyn_lds(fn, lds_max, "resblock_bwd_kernel")) return rc;
   void* args[] = {&a};
   (void)hipLaunchKernel(fn, dim3(a.nwg), dim3(256), args, lds, s);
   VQA_LAUNCHED("resblock_bwd_kernel");

@@ -1,13 +1,16 @@
-// vqa_runtime.hip — error reporting, losses and the Keras-Adam optimizer kernel (gfx950).
+// vqa_runtime.hip — error reporting, launch support, losses and the Keras-Adam optimizer kernel (gfx950).
 //
 //   vqa_mse_loss   : keras MeanSquaredError(reduction=NONE) + tf.reduce_mean (vqvae.py:91,125) fused with
 //                    its gradient and the spectral-loss gradient add.
 //   vqa_adam_keras : keras.optimizers.Adam() defaults as applied by TF's ApplyAdam (vqvae.py:144,362):
 //                    one launch over the flat fp32 parameter buffer of all levels.
-#include "vqa_common.h"
+#include "vqa_launch.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <utility>
 
 namespace vqa {
 
@@ -18,6 +21,49 @@ void set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+// ---- launch support (vqa_launch.h)
+int cu_count() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) {
+      (void)hipGetLastError();
+      v = 256;
+    }
+    return v;
+  }();
+  return n;
+}
+
+static std::mutex g_launch_mu;  // guards the two stores below
+
+int raise_dyn_lds(const void* fn, size_t bytes, const char* what) {
+  if (bytes <= 65536) return VQA_OK;
+  static std::map<const void*, size_t> raised;
+  std::lock_guard<std::mutex> lock(g_launch_mu);
+  size_t& have = raised[fn];
+  if (bytes <= have) return VQA_OK;
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("%s: cannot reserve %zu B of LDS: %s", what, bytes, hipGetErrorString(e));
+    return VQA_E_UNSUPPORTED;
+  }
+  have = bytes;
+  return VQA_OK;
+}
+
+int resident_per_cu(const void* fn, int threads, size_t lds) {
+  static std::map<std::pair<const void*, size_t>, int> resident;
+  std::lock_guard<std::mutex> lock(g_launch_mu);
+  int& n = resident[{fn, lds}];
+  if (n == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, lds) != hipSuccess || n < 1)) {
+    (void)hipGetLastError();
+    n = 1;
+  }
+  return n;
 }
 
 __global__ __launch_bounds__(256) void mse_kernel(const float* x, const float* r, const float* extra, float* dr,

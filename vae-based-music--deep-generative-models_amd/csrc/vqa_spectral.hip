@@ -16,7 +16,7 @@
 // ||S_x||) is known only after every frame of the item is done, so a second kernel reduces the partial sums
 // per (item, resolution) and a third overlap-adds the frame gradients (fixed summation order:
 // deterministic) and applies the scales. No atomics, no host sync, graph-capturable.
-#include "vqa_common.h"
+#include "vqa_launch.h"
 #include <utility>
 #include <algorithm>
 
@@ -1055,37 +1055,13 @@ template <int N, int MODE>
 static int launch_pairs(const SpecPairArgs& pa, hipStream_t s) {
   constexpr int FPI = kSpecWaves;  // frame pairs (one per wave) in flight per workgroup
   const size_t lds = (size_t)N * sizeof(f32x2) + (size_t)N * sizeof(float) + (size_t)FPI * fpad<N>() * sizeof(f32x2);
-  static size_t lds_set = 0;
-  if (lds > 65536 && lds > lds_set) {
-    if (hipFuncSetAttribute((const void*)spec_pair_kernel<N, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("spectral: cannot reserve %zu B of LDS", lds);
-      return VQA_E_UNSUPPORTED;
-    }
-    lds_set = lds;
-  }
+  const void* fn = (const void*)spec_pair_kernel<N, MODE>;
+  if (int rc = raise_dyn_lds(fn, lds, "spec_pair_kernel")) return rc;
   // persistent: as many workgroups as fit on the chip at once (LDS-bound), each wave walking its pairs with the
   // next pair's samples prefetched; the tables are loaded once per workgroup
   const int npairs = (pa.B * pa.F + 1) / 2;
   const int groups = (npairs + FPI - 1) / FPI;
-  static int cus = [] {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    return v;
-  }();
-  static size_t occ_lds = 0;  // resident workgroups per CU (LDS and registers), queried once per LDS size
-  static int per_cu = 1;
-  if (occ_lds != lds) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)spec_pair_kernel<N, MODE>, 64 * kSpecWaves,
-                                                     lds) != hipSuccess || per_cu <= 0) {
-      (void)hipGetLastError();
-      per_cu = 1;
-    }
-    occ_lds = lds;
-  }
-  const int grid = std::min(groups, cus * per_cu);
+  const int grid = std::min(groups, cu_count() * resident_per_cu(fn, 64 * kSpecWaves, lds));
   hipLaunchKernelGGL((spec_pair_kernel<N, MODE>), dim3(grid), dim3(64 * kSpecWaves), lds, s, pa);
   VQA_LAUNCHED("spec_pair_kernel");
   return VQA_OK;
@@ -1099,33 +1075,10 @@ static int launch_pairs4(const SpecPairArgs& pa, hipStream_t s) {
   constexpr int W = spec4_waves<N>();
   const size_t lds = (size_t)(S4::P * S4::PITCH + 64) * sizeof(f32x2) + (size_t)N * sizeof(float) +
                      (size_t)W * S4::BUF * sizeof(f32x2);
-  static size_t lds_set = 0;
-  if (lds > 65536 && lds > lds_set) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("spectral: cannot reserve %zu B of LDS", lds);
-      return VQA_E_UNSUPPORTED;
-    }
-    lds_set = lds;
-  }
+  if (int rc = raise_dyn_lds(fn, lds, "spec_pair4_kernel")) return rc;
   const int npairs = (pa.B * pa.F + 1) / 2;
   const int groups = (npairs + W - 1) / W;
-  static int cus = [] {
-    int dev = 0, v = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    return v;
-  }();
-  static size_t occ_lds = 0;
-  static int per_cu = 1;
-  if (occ_lds != lds) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * W, lds) != hipSuccess || per_cu <= 0) {
-      (void)hipGetLastError();
-      per_cu = 1;
-    }
-    occ_lds = lds;
-  }
-  const int grid = std::min(groups, cus * per_cu);
+  const int grid = std::min(groups, cu_count() * resident_per_cu(fn, 64 * W, lds));
   hipLaunchKernelGGL((spec_pair4_kernel<N, MODE>), dim3(grid), dim3(64 * W), lds, s, pa);
   VQA_LAUNCHED("spec_pair4_kernel");
   return VQA_OK;
