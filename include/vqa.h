@@ -328,6 +328,26 @@ int vqa_corpus_batch(const void* corpus, int64_t corpus_len, int pcm, const int6
                      uint64_t seed, const int64_t* counter /* may be NULL */, int64_t step, int rank, int world,
                      int shuffle, vqa_stream_t stream);
 
+/* ---- waveform -> 16-bit PCM (the way out of the device: the reference listens to what it decodes,
+ *      utils/tf_utils.py:129-154,196-226 and the monitors' log_input_output_audio) -------------------------
+ * The inverse of the feed's load (x = i * 2^-15), fused with the crop-and-place step of chunked decoding. For
+ * each of the B rows it takes the n fp32 samples from x + b*ldx + x0 and writes int16 to out + b*ldo + o0:
+ *   v   = (x * gain) * 32768                   two fp32 products, each rounded (no fma contraction)
+ *   r   = v rounded to the nearest integer, halves to even
+ *   pcm = 0 if v is NaN, else min(max(r, -32768), 32767)
+ *   clipped[b] += the number of the row's n samples with r outside [-32768, 32767] or NaN   (int32, may be NULL)
+ * With gain 1 every int16 i written as i * 2^-15 comes back as i. The kernel adds to clipped and never zeroes it,
+ * so the launches of several chunks sum into one count per row (the caller zeroes it first); the count is an
+ * integer sum of per-wave totals and does not depend on the order they arrive in.
+ * Memory contract: only the n samples [x0, x0 + n) of every row of x are read and only [o0, o0 + n) of every row
+ * of out are written. x0, o0, ldx, ldo and n are arbitrary: a row's 16-byte stores of 8 samples are aligned by a
+ * scalar head and tail, and its 16-byte loads need only a float's alignment.
+ * VQA_E_INVALID_ARG before any launch (messages start "pcm_encode:"): a null x or out; B or n not positive (B at
+ * most 65535); a negative x0 or o0; x0 + n > ldx or o0 + n > ldo; x not 4-byte, out not 2-byte or clipped not
+ * 4-byte aligned; a gain that is not finite and >= 0. */
+int vqa_pcm_encode(const float* x, int64_t ldx, int16_t* out, int64_t ldo, int B, int64_t x0, int64_t o0, int64_t n,
+                   float gain, int32_t* clipped /* may be NULL */, vqa_stream_t stream);
+
 /* ---- multi-resolution spectral loss --------------------------------------------------------------
  * Replaces vqvae.py:309-326 (_multispectral_loss) over data_utils.py:25-30 (spectral = |tf.signal.stft|)
  * and data_utils.py:33-40 (norm = tf.norm 'fro'), plus its GradientTape backward (vqvae.py:143):

@@ -162,6 +162,46 @@ def read_wav_pcm(file, sr=None, offset=0.0, duration=None):
     return a.reshape(n, C), 8 * width, rate
 
 
+def write_wav(file, pcm, sr):
+    """The inverse of read_wav_pcm for 16-bit data: pcm, int16 (n,) or (n, C) frames — a numpy array or a tensor
+    (a device tensor is copied to the host once) — written as an integer-PCM WAV of rate `sr` through the standard
+    library's `wave`. Anything but int16 is a ValueError: nothing is scaled or rounded here (VQVAE.render and
+    vqa_pcm_encode do that on the device)."""
+    a = pcm.detach().cpu().numpy() if isinstance(pcm, torch.Tensor) else np.asarray(pcm)
+    if a.dtype != np.int16:
+        raise ValueError(f"write_wav: 16-bit PCM is int16 (got {a.dtype})")
+    if a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[1] < 1):
+        raise ValueError(f"write_wav: frames are (n,) or (n, C) (got shape {a.shape})")
+    if int(sr) <= 0:
+        raise ValueError(f"write_wav: sample rate {sr}")
+    with wave.open(str(file), "wb") as w:
+        w.setnchannels(1 if a.ndim == 1 else a.shape[1])
+        w.setsampwidth(2)
+        w.setframerate(int(sr))
+        w.writeframes(np.ascontiguousarray(a, dtype="<i2").tobytes())
+
+
+def save_wavs(pcm, directory, sr, labels=None, prefix="sample"):
+    """One mono WAV per row of pcm, int16 (B, n) (VQVAE.render's / VQVAESampler.sample_audio's result; a device
+    tensor is copied once): directory/prefix_{i}.wav, or with labels directory/prefix_{i}_{genre}.wav, genre =
+    IDX_TO_GENRES[labels[i]] (utils/tf_utils.py:196-226 generate_and_save_waves names its files by genre too).
+    The directory is created. Returns the paths."""
+    a = pcm.detach().cpu().numpy() if isinstance(pcm, torch.Tensor) else np.asarray(pcm)
+    if a.ndim != 2:
+        raise ValueError(f"save_wavs: pcm is (B, n) (got shape {a.shape})")
+    if labels is not None:
+        labels = [int(v) for v in (labels.tolist() if hasattr(labels, "tolist") else labels)]
+        if len(labels) != a.shape[0]:
+            raise ValueError(f"save_wavs: {len(labels)} labels for {a.shape[0]} rows")
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for i in range(a.shape[0]):
+        name = f"{prefix}_{i}.wav" if labels is None else f"{prefix}_{i}_{IDX_TO_GENRES[labels[i]]}.wav"
+        paths.append(os.path.join(directory, name))
+        write_wav(paths[-1], a[i], sr)
+    return paths
+
+
 def load_audio(file, sr=22050, offset=0.0, duration=None, mono=False):
     """data_utils.py:43-48 (librosa.load there): -> (C, n) float32, a sample being int / 2^(bits-1) (8-bit data is
     unsigned with a 128 offset), exactly for up to 24 bits. Integer-PCM WAV of 8, 16, 24 or 32 bits through the

@@ -193,6 +193,37 @@ class Decoder(Layer):
         self._saved = x if save else None
         return self.out.forward(x, self.cdt, out_dtype=torch.float32)
 
+    def receptive_reach(self):
+        """(reach, hop) of the built decoder: `hop` output samples per input code, and `reach` an upper bound, in
+        output samples, on how far a cut of the input sequence is felt — decoding codes [a, b) alone gives the
+        samples the whole sequence gives everywhere except within `reach` samples of a cut that is not a true end
+        of the sequence. Walks the layers in forward order with the library's own SAME padding
+        (vqa_same_pad_left), e = the samples next to a cut that differ, at the current rate:
+          Conv1D (stride 1, K taps, dilation d): output t reads inputs t - pl .. t + pr with pl the left pad and
+            pr = (K - 1) d - pl, so e <- e + max(pl, pr) (the pre conv, conv_a and conv_b of every residual block —
+            the skip path adds nothing — and the output conv);
+          Conv1DTranspose (stride s, K taps, left pad pl): output o reads inputs ceil((o + pl - K + 1) / s) ..
+            floor((o + pl) / s), so the first s e + K - s - pl and the last s e + pl outputs differ:
+            e <- s e + max(K - s - pl, pl), hop <- s hop.
+        The fused tail (vqa_dtail) is the last transposed conv followed by the output conv: the same two steps."""
+        T = 1 << 20  # the pads of these layers do not depend on the length (stride-1 convs; T_out = s T_in)
+        e, hop = 0, 1
+
+        def conv(c, e):
+            assert c.s == 1, f"{c.name}: the decoder's Conv1D layers have stride 1"
+            pl = V.same_pad_left(T, c.K, 1, c.d)
+            return e + max(pl, (c.K - 1) * c.d - pl)
+
+        for blk in self.blocks:
+            e = conv(blk.pre, e)
+            for res, up in zip(blk.res, blk.up):
+                for rb in res.blocks:
+                    e = conv(rb.conv_b, conv(rb.conv_a, e))
+                pl = V.same_pad_left(up.s * T, up.K, up.s, 1)
+                e = up.s * e + max(up.K - up.s - pl, pl)
+                hop *= up.s
+        return conv(self.out, e), hop
+
     def backward(self, dy):
         saved = self._saved
         self._saved = None

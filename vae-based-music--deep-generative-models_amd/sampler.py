@@ -68,6 +68,27 @@ class VQVAESampler:
                                    hop_length=hops[level], temperature=temperature, top_k=top_k)
         return zs
 
+    def sample_audio(self, n_samples, vqvae, y_genre=None, seed=0, *, level=0, chunk_codes=4096, gain=1.0,
+                     **sample_kwargs):
+        """sample() followed by the VQ-VAE's decoder, as the reference does after every sampling run
+        (utils/tf_utils.py:196-226 generate_and_save_waves: model.decode(codes, level)): draws the codes of every
+        level (sample_kwargs: total_length, hop_lengths, temperature, top_k — the draw is sample()'s, seeds
+        included), then renders level `level`'s codes to 16-bit PCM in chunks of chunk_codes codes (VQVAE.render).
+        Returns (pcm (n_samples, codes * hop) int16, clipped (n_samples,) int32, zs). The sampler and the VQ-VAE
+        must have the same levels and hop lengths; codes outside the codebook — the start token of a prior whose
+        bins exceed num_embeddings — raise VQVAE.render's ValueError."""
+        if vqvae.levels != self.levels:
+            raise ValueError(f"sample_audio: the VQ-VAE has {vqvae.levels} levels, the sampler {self.levels}")
+        hops = [int(h) for h in vqvae.decode_hops]
+        if hops != [int(h) for h in self.hop_lengths]:
+            raise ValueError(f"sample_audio: the VQ-VAE's hop lengths {hops} differ from the sampler's "
+                             f"{[int(h) for h in self.hop_lengths]}")
+        if not 0 <= int(level) < self.levels:
+            raise ValueError(f"sample_audio: level {level} outside [0, {self.levels})")
+        zs = self.sample(n_samples, y_genre=y_genre, seed=seed, **sample_kwargs)
+        pcm, clipped = vqvae.render(zs[level], level, chunk_codes=chunk_codes, gain=gain)
+        return pcm, clipped, zs
+
     def _plan(self, total_length, hop_lengths):
         """(codes per level, hop per level) of a sample() call, checked before anything is drawn: every window
         start and end of a conditioned level must fall on a code of the level above (Prior.get_cond)."""

@@ -43,7 +43,7 @@ EXPORTED = [
     "vqa_axpy", "vqa_dropout", "vqa_scale_f32", "vqa_tf_mix", "vqa_attn_fwd", "vqa_attn_bwd", "vqa_head_wt",
     "vqa_head_fwd", "vqa_head_bwd_workspace", "vqa_head_bwd", "vqa_rowsum_workspace", "vqa_rowsum", "vqa_prior_decode_cache_bytes",
     "vqa_prior_decode", "vqa_prior_decode_primed",
-    "vqa_corpus_steps_per_epoch", "vqa_corpus_batch",
+    "vqa_corpus_steps_per_epoch", "vqa_corpus_batch", "vqa_pcm_encode",
 ]
 
 
@@ -148,6 +148,8 @@ _SIGS = {
     # device-resident corpus feed
     "vqa_corpus_steps_per_epoch": (_L, [_L, _I, _I]),
     "vqa_corpus_batch": (_I, [_P, _L, _I, _P, _P, _L, _P, _P, _P, _I, _L, _U, _P, _L, _I, _I, _I, _P]),
+    # waveform -> int16 PCM
+    "vqa_pcm_encode": (_I, [_P, _L, _P, _L, _I, _L, _L, _L, _F, _P, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -572,6 +574,26 @@ def corpus_batch(corpus, corpus_len, starts, labels, x, labels_out=None, index_o
     _check(lib().vqa_corpus_batch(ptr(corpus), corpus_len, pcm, ptr(starts), ptr(labels), M, ptr(x), ptr(labels_out),
                                   ptr(index_out), B, T, int(seed), ptr(counter), int(step), int(rank), int(world),
                                   int(bool(shuffle)), stream()), "vqa_corpus_batch")
+
+
+def pcm_encode(x, out, x0=0, o0=0, n=None, gain=1.0, clipped=None):
+    """fp32 waveform -> int16 PCM with crop and placement (vqa_pcm_encode, include/vqa.h): x is the (B, ldx) or
+    (B, ldx, 1) fp32 source (1-D: one row), out the (B, ldo) int16 destination; samples [x0, x0 + n) of every row of
+    x go to [o0, o0 + n) of the same row of out as clamp(round_half_even(x * gain * 32768)), NaN as 0. n defaults to
+    the rest of x's rows. clipped (B,) int32 is added to, never zeroed: the samples that were clamped or NaN."""
+    if x.dtype != torch.float32 or out.dtype != torch.int16:
+        raise VQAError(f"pcm_encode: x is float32 and out int16 (got {x.dtype}, {out.dtype})")
+    B = x.shape[0] if x.dim() > 1 else 1
+    ldx = x.numel() // max(B, 1)
+    Bo = out.shape[0] if out.dim() > 1 else 1
+    ldo = out.numel() // max(Bo, 1)
+    if Bo != B:
+        raise VQAError(f"pcm_encode: x has {B} rows, out {Bo}")
+    if clipped is not None and (clipped.dtype != torch.int32 or clipped.numel() != B):
+        raise VQAError(f"pcm_encode: clipped holds {B} int32 entries")
+    n = ldx - int(x0) if n is None else int(n)
+    _check(lib().vqa_pcm_encode(ptr(x), ldx, ptr(out), ldo, B, int(x0), int(o0), n, float(gain), ptr(clipped),
+                                stream()), "vqa_pcm_encode")
 
 
 def _int_array(vals):

@@ -102,6 +102,39 @@ def get_vqvae(input_shape, encoder, decoder, vq, level=0, **kwargs):
     return LevelModel(input_shape, encoder, decoder, vq, level, **kwargs)
 
 
+def decoder_halo(decoder: Decoder) -> int:
+    """Codes on each side of a core range that influence that core's audio: the decoder's receptive reach
+    (Decoder.receptive_reach, output samples) rounded up to whole codes."""
+    reach, hop = decoder.receptive_reach()
+    return -(-reach // hop)
+
+
+def decode_halo_for(level, down_depth, strides, residual_width=64, residual_depth=4, dilation_factor=1, latent_dim=64,
+                    channels=1) -> int:
+    """VQVAE.decode_halo(level) of a model with this configuration, from the layer list alone (built on the host
+    with no weights: needs no GPU)."""
+    dec = Decoder(output_dim=channels, embed_width=latent_dim, residual_width=residual_width,
+                  residual_depth=residual_depth, depth=level + 1, down_depth=list(down_depth)[:level + 1],
+                  strides=list(strides)[:level + 1], dilation_factor=dilation_factor)
+    dec.build(ParamStore(), f"dec{level}", latent_dim, torch.float32)
+    return decoder_halo(dec)
+
+
+def decode_plan(total_codes, chunk_codes, halo):
+    """The chunks of a bounded-memory decode of `total_codes` codes: a list of (in_lo, in_hi, core_lo, core_hi).
+    The cores [core_lo, core_hi) are consecutive ranges of at most chunk_codes codes that tile [0, total_codes)
+    exactly once; [in_lo, in_hi) is the core widened by `halo` codes on each side and clamped to the sequence. A
+    chunk next to an end of the sequence therefore reaches that end itself — nothing is padded, and the true ends
+    get the decoder's own zero padding, as in a whole-sequence decode."""
+    total, chunk, halo = int(total_codes), int(chunk_codes), int(halo)
+    if total <= 0 or chunk <= 0:
+        raise ValueError(f"decode_plan: total_codes {total} and chunk_codes {chunk} must be positive")
+    if halo < 0:
+        raise ValueError(f"decode_plan: negative halo {halo}")
+    return [(max(0, lo - halo), min(total, min(lo + chunk, total) + halo), lo, min(lo + chunk, total))
+            for lo in range(0, total, chunk)]
+
+
 class VQVAE:
     def __init__(self, input_shape, levels, latent_dim, down_depth, strides, num_embeddings=128, residual_width=64,
                  residual_depth=4, dilation_factor=1, train_variance=1.0, *, dtype="bf16", device="cuda",
@@ -572,6 +605,78 @@ class VQVAE:
 
     def decode(self, zq, level=0):
         return self.decode_level(zq, level)
+
+    # ------------------------------------------------------------------ bounded-memory decode, PCM out
+    def decode_halo(self, level) -> int:
+        """Codes on each side of a core range of level `level` that influence that core's audio (an upper bound,
+        derived from the level's decoder layers: Decoder.receptive_reach)."""
+        return decoder_halo(self.decoders[level])
+
+    @property
+    def decode_hops(self) -> List[int]:
+        """Audio samples per code of every level's decoder (8 / 32 / 128 at down_depth [3, 2, 2])."""
+        return [self.decoders[l].receptive_reach()[1] for l in range(self.levels)]
+
+    def _checked_codes(self, zq, what) -> torch.Tensor:
+        """zq as a (B, T) int64 device tensor with every code in [0, num_embeddings), or ValueError — settled here
+        (one device sync for the minimum and maximum) before any kernel of the decode is launched."""
+        if not isinstance(zq, torch.Tensor):
+            zq = torch.as_tensor(np.asarray(zq))
+        if zq.dtype != torch.int64:
+            raise ValueError(f"{what}: codes must be int64 (got {zq.dtype})")
+        if zq.dim() != 2 or zq.numel() == 0:
+            raise ValueError(f"{what}: codes must be a non-empty (B, T) tensor (got shape {tuple(zq.shape)})")
+        zq = zq.to(self.device)
+        lo, hi = (int(v) for v in torch.aminmax(zq))
+        K = self.num_embeddings
+        if lo < 0 or hi >= K:
+            bad = lo if lo < 0 else hi
+            hint = (f"; {K} is the start token of a prior built with bins = num_embeddings + 1: strip it before "
+                    f"decoding") if bad == K else ""
+            raise ValueError(f"{what}: code {bad} outside [0, {K}){hint}")
+        return zq
+
+    def _decode_chunks(self, zq, level, chunk_codes):
+        """(in_lo, core_lo, core_hi, audio) of every chunk of decode_plan, audio = the decoder's fp32 (B, L hop, 1)
+        output for the codes [in_lo, in_hi) — one chunk's activations alive at a time, nothing saved."""
+        dec, vq = self.decoders[level], self.vqs[level]
+        B, T = zq.shape
+        for in_lo, in_hi, core_lo, core_hi in decode_plan(T, chunk_codes, decoder_halo(dec)):
+            idx = zq[:, in_lo:in_hi].contiguous()
+            q = torch.empty(B, in_hi - in_lo, self.latent_dim, dtype=self.cdt, device=self.device)
+            V.embedding_fwd(vq.ET, idx, q)  # one_hot(zq) @ E^T as a row gather, straight into the compute dtype
+            yield in_lo, core_lo, core_hi, dec.forward(q)
+
+    def decode_chunked(self, zq, level=0, chunk_codes=4096):
+        """decode(zq, level) with bounded memory: the sequence is decoded in cores of chunk_codes codes, each with
+        decode_halo(level) codes of context on both sides (decode_plan), so no activation is longer than
+        chunk_codes + 2 halo codes. Returns the fp32 (B, T hop, 1) waveform; zq is (B, T) int64 with every code in
+        [0, num_embeddings) (ValueError otherwise, before anything is launched)."""
+        zq = self._checked_codes(zq, "decode_chunked")
+        hop = self.decoders[level].receptive_reach()[1]
+        y = torch.empty(zq.shape[0], zq.shape[1] * hop, 1, dtype=torch.float32, device=self.device)
+        with torch.no_grad():
+            for in_lo, core_lo, core_hi, r in self._decode_chunks(zq, level, chunk_codes):
+                y[:, core_lo * hop:core_hi * hop] = r[:, (core_lo - in_lo) * hop:(core_hi - in_lo) * hop]
+        return y
+
+    def render(self, zq, level=0, chunk_codes=4096, gain=1.0):
+        """Codes to 16-bit PCM: -> (pcm (B, T hop) int16, clipped (B,) int32), both on the device. The chunks of
+        decode_chunked, each core cropped out of its chunk, scaled by `gain`, rounded half to even, clamped and
+        placed by one vqa_pcm_encode launch; clipped[b] counts the samples of item b that were clamped (or NaN).
+        The full-length fp32 waveform is never formed."""
+        zq = self._checked_codes(zq, "render")
+        gain = float(gain)
+        if not (np.isfinite(gain) and gain >= 0.0):
+            raise ValueError(f"render: gain {gain} must be finite and >= 0")
+        hop = self.decoders[level].receptive_reach()[1]
+        pcm = torch.empty(zq.shape[0], zq.shape[1] * hop, dtype=torch.int16, device=self.device)
+        clipped = torch.zeros(zq.shape[0], dtype=torch.int32, device=self.device)
+        with torch.no_grad():
+            for in_lo, core_lo, core_hi, r in self._decode_chunks(zq, level, chunk_codes):
+                V.pcm_encode(r, pcm, x0=(core_lo - in_lo) * hop, o0=core_lo * hop, n=(core_hi - core_lo) * hop,
+                             gain=gain, clipped=clipped)
+        return pcm, clipped
 
     # ------------------------------------------------------------------ training loop / state
     def fit(self, x=None, y=None, batch_size=32, epochs=1, shuffle=True, seed=0, verbose=0):
