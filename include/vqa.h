@@ -328,6 +328,38 @@ int vqa_corpus_batch(const void* corpus, int64_t corpus_len, int pcm, const int6
                      uint64_t seed, const int64_t* counter /* may be NULL */, int64_t step, int rank, int world,
                      int shuffle, vqa_stream_t stream);
 
+/* ---- device-resident code feed (the prior's counterpart: replaces re-running the frozen VQ-VAE encoder on every
+ *      prior step, prior.py:257-260) ---------------------------------------------------------------------------
+ * The corpus is every track's codes of one level back to back in device memory (int16 or int32, `width`), and —
+ * for a prior conditioned on the level above — that level's codes of the same tracks in the same order, `rate`
+ * codes of this level per code of the upper one, so that code t of this level lies under code t / rate of the upper
+ * level. starts[i] = the first code of window i in `codes`, labels[i] its class (may be NULL), i in [0, M).
+ * The window of item b is resolved exactly as vqa_corpus_batch resolves it (same g, S, epoch, pos, slot k and
+ * permutation key (seed, epoch, VQA_FEED_PERM_LEVEL)); one launch then writes
+ *   z[b][t]       = codes[starts[i] + t]             t < T         z is (B, T) int64
+ *   z_upper[b][u] = upper[starts[i] / rate + u]      u < T / rate  z_upper is (B, T / rate) int64 (with `upper`)
+ *   labels_out[b] = labels[i]                        (nullable)
+ *   index_out[b]  = i                                (nullable)
+ * widening the stored codes to int64: int16 is zero-extended and int32 loses its sign bit, so a negative value is
+ * never written (the step gathers embedding rows with these codes).
+ * Memory contract: `codes` and `upper` (16-byte aligned) are readable up to codes_len / upper_len codes rounded up
+ * to a multiple of 16 bytes; a window is read through aligned 16-byte loads of the chunks that enclose it and
+ * nothing else is touched. Each chosen window is checked once per item on the device: 0 <= starts[i],
+ * starts[i] + T <= codes_len and, with `upper`, starts[i] % rate == 0 and starts[i] / rate + T / rate <= upper_len.
+ * A window that fails is never read: both of its rows are zeros and index_out[b] = -1.
+ * VQA_E_INVALID_ARG before any launch (messages start "code_batch:"): a null codes, starts or z; B, T or M not
+ * positive (B at most 65535); rate < 1; T not a multiple of rate; upper without z_upper or the reverse; width not
+ * one of the two values; codes or upper not 16-byte aligned; z, z_upper, labels_out or index_out not 8-byte aligned
+ * (the rows' 16-byte stores are aligned by a scalar head and tail, whatever T is); world < 1; rank outside
+ * [0, world); M < B*world; labels_out without labels; a negative step, codes_len or upper_len. */
+enum { VQA_CODE_I16 = 0, VQA_CODE_I32 = 1 };
+int vqa_code_batch(const void* codes, int64_t codes_len, const void* upper /* may be NULL */, int64_t upper_len,
+                   int rate, int width, const int64_t* starts, const int64_t* labels /* may be NULL */, int64_t M,
+                   int64_t* z, int64_t* z_upper /* NULL exactly when upper is */,
+                   int64_t* labels_out /* may be NULL */, int64_t* index_out /* may be NULL */, int B, int64_t T,
+                   uint64_t seed, const int64_t* counter /* may be NULL */, int64_t step, int rank, int world,
+                   int shuffle, vqa_stream_t stream);
+
 /* ---- waveform -> 16-bit PCM (the way out of the device: the reference listens to what it decodes,
  *      utils/tf_utils.py:129-154,196-226 and the monitors' log_input_output_audio) -------------------------
  * The inverse of the feed's load (x = i * 2^-15), fused with the crop-and-place step of chunked decoding. For

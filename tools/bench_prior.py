@@ -11,6 +11,17 @@ Synthetic codes (uniform over the codebook), random-init weights. The cpu leg ti
 The sample leg takes the primed decode's options: --prime-len P (the first P positions are given, random codes;
 P = --sample-len times the primed positions alone, head skipped), --temperature, --top-k, and --repeats R (R timed
 launches in one process; ms_per_position is their median, ms_per_position_repeats lists them).
+  feed  : (--only feed; never part of the default run) the config-4 train step fed three ways, in one process:
+          (a) captured, codes copied in (the `train` leg's step), (b) captured on a code_feed.CodeFeed over a
+          device-resident corpus of random codes (--tracks tracks of 4 ctx codes, windows hopping by ctx / 2),
+          (c) eager from raw audio through the frozen VQ-VAE encoder (config 2's level 2, window ctx * 128 samples;
+          --audio-ctx for a shorter window), with the eager step on codes beside it. (a) and (b) alternate for
+          --repeats rounds of --steps steps, each round between two device events after a synchronize; the JSON
+          line holds every round, the median and the range.
+  feed-kernel : (--only feed-kernel) --steps CodeFeed.next() calls at that shape and nothing else, for a
+          `rocprofv3 --kernel-trace --stats` run of its own.
+  encode-mem  : (--only encode-mem) peak torch.cuda.max_memory_allocated of encode_level and of encode_chunked
+          for one item of 2^20 samples at level 0 of config 2.
 """
 import argparse
 import json
@@ -22,6 +33,124 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "vae-based-music--deep-generative-models_amd"), ROOT]
 
 import torch  # noqa: E402
+
+
+def _code_feed(a, dev):
+    """A one-level corpus of random codes (the top level: unconditioned) and its feed at the config-4 shape."""
+    import numpy as np
+    from code_feed import CodeCorpus, CodeFeed
+    rng = np.random.default_rng(1)
+    tracks = [rng.integers(0, a.bins - 1, 4 * a.ctx) for _ in range(a.tracks)]
+    corpus = CodeCorpus.from_codes([tracks], None, [128], a.bins - 1, device=dev)
+    return CodeFeed(corpus, 0, n_ctx=a.ctx, batch_size=a.batch, hop=a.ctx // 2, seed=1)
+
+
+def _rounds(fn, steps, rounds):
+    """ms/step of `rounds` rounds of `steps` calls, each between two device events on an idle stream."""
+    out = []
+    for _ in range(rounds):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / steps)
+    return out
+
+
+def _stats(v):
+    s = sorted(v)
+    return {"median": round(s[len(s) // 2], 4), "min": round(s[0], 4), "max": round(s[-1], 4),
+            "rounds": [round(x, 4) for x in v]}
+
+
+def feed_mode(a):
+    from prior import Prior
+    from vqvae import VQVAE
+    kw = dict(width=128, depth=6, heads=2, blocks=4, attn_stacks=1, drop_out_rate=0.0)
+    dev = torch.device("cuda:0")
+
+    def prior(vq=None, ctx=a.ctx):
+        return Prior(2, [(ctx * 16,), (ctx * 4,), (ctx,)], a.bins, [3, 2, 2], [2, 2, 2], vq, kw, None, dtype=a.dtype,
+                     device="cuda")
+
+    g = torch.Generator(device=dev).manual_seed(1)
+    codes = torch.randint(0, a.bins - 1, (a.batch, a.ctx), device=dev, generator=g)
+    pa, pb = prior(), prior()
+    feed = _code_feed(a, dev)
+    pa.capture_train_step(codes, warmup=a.warmup)
+    pb.capture_train_step(feed, warmup=a.warmup)
+    for _ in range(3):  # the first replays upload the graphs
+        pa.train_step(codes)
+        pb.train_step(feed)
+    ra, rb = [], []
+    for _ in range(max(1, a.repeats)):  # alternating, so that drift of the device's state falls on both
+        ra += _rounds(lambda: pa.train_step(codes), a.steps, 1)
+        rb += _rounds(lambda: pb.train_step(feed), a.steps, 1)
+    out = {"metric": "ms/step prior train step by feed (SMALL_PRIOR, config 4)", "unit": "ms/step", "n_gpus": 1,
+           "batch": a.batch, "ctx": a.ctx, "bins": a.bins, "dtype": a.dtype, "steps_per_round": a.steps,
+           "windows": len(feed.starts_host), "feed_step": feed.step,
+           "a_captured_codes_copied_in": _stats(ra), "b_captured_code_feed": _stats(rb)}
+    del pa, pb
+    torch.cuda.empty_cache()
+    # eager legs: from codes, and from raw audio through the frozen encoder (level 2 of config 2)
+    actx = a.audio_ctx or a.ctx
+    T = actx * 128
+    vq = VQVAE((T, 1), 3, 64, [3, 2, 2], [2, 2, 2], num_embeddings=a.bins - 1, residual_width=64, residual_depth=4,
+               dilation_factor=3, dtype=a.dtype, device="cuda")
+    pc = prior(vq, actx)
+    x = torch.rand(a.batch, T, 1, device=dev, generator=g) * 2 - 1
+    ec = codes[:, :actx].contiguous()
+    n = max(2, a.steps // 2)
+    for _ in range(2):
+        pc.train_step(ec)
+        pc.train_step(x)
+    out["audio_ctx"] = actx
+    out["eager_codes"] = _stats(_rounds(lambda: pc.train_step(ec), n, max(1, a.repeats)))
+    out["c_eager_raw_audio"] = _stats(_rounds(lambda: pc.train_step(x), n, max(1, a.repeats)))
+    out["c_over_b"] = round(out["c_eager_raw_audio"]["median"] / out["b_captured_code_feed"]["median"], 3)
+    print(json.dumps(out), flush=True)
+
+
+def feed_kernel_mode(a):
+    dev = torch.device("cuda:0")
+    feed = _code_feed(a, dev)
+    for _ in range(a.steps):
+        feed.next()
+    torch.cuda.synchronize()
+    print(json.dumps({"mode": "feed-kernel", "launches": a.steps, "batch": a.batch, "ctx": a.ctx,
+                      "bytes_per_launch": a.batch * a.ctx * (8 + feed.corpus.codes[0].element_size()),
+                      "step": feed.step}), flush=True)
+
+
+def encode_mem_mode(a):
+    from vqvae import VQVAE
+    dev = torch.device("cuda:0")
+    T = 1 << 20
+    m = VQVAE((T, 1), 3, 64, [3, 2, 2], [2, 2, 2], num_embeddings=a.bins - 1, residual_width=64, residual_depth=4,
+              dilation_factor=3, dtype=a.dtype, device="cuda")
+    x = torch.rand(1, T, 1, device=dev) * 2 - 1
+    out = {"mode": "encode-mem", "samples": T, "level": 0, "dtype": a.dtype, "halo_codes": m.encode_halo(0)}
+    whole = None
+    for name, fn in (("encode_level", lambda: m.encode_level(x, 0)),
+                     ("encode_chunked_65536", lambda: m.encode_chunked(x, 0, chunk_samples=1 << 16)),
+                     ("encode_chunked_262144", lambda: m.encode_chunked(x, 0, chunk_samples=1 << 18))):
+        fn()  # every shape warmed (workspaces, kernels)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        z = fn()
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        out[name] = {"peak_MiB": round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1),
+                     "ms": round(el * 1e3, 2)}
+        whole = z if whole is None else whole
+        out[name]["equals_encode_level"] = bool(torch.equal(z, whole))
+    print(json.dumps(out), flush=True)
 
 
 def main():
@@ -40,7 +169,11 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--only", default="")
+    ap.add_argument("--tracks", type=int, default=32)
+    ap.add_argument("--audio-ctx", type=int, default=0)
     a = ap.parse_args()
+    if a.only in ("feed", "feed-kernel", "encode-mem"):
+        return {"feed": feed_mode, "feed-kernel": feed_kernel_mode, "encode-mem": encode_mem_mode}[a.only](a)
     from prior import Prior, FMHABasedAutoregressiveModel
     kw = dict(width=128, depth=6, heads=2, blocks=4, attn_stacks=1, drop_out_rate=0.0)
     dev = torch.device("cuda:0")

@@ -146,6 +146,45 @@ class Encoder(Layer):
             dy = self.blocks[b].backward(dy, need_dx=(b > 0 or need_dx))
         return dy
 
+    def receptive_reach(self):
+        """(reach, hop) of the built encoder: `hop` input samples per output code, and `reach` an upper bound, in
+        output codes, on how far a cut of the input is felt — encoding samples [a, b) alone (a, b and the length
+        multiples of hop) gives the codes the whole sequence gives everywhere except within `reach` codes of a cut
+        that is not a true end of the sequence. The mirror of Decoder.receptive_reach: walks the layers in forward
+        order with the library's own SAME padding (vqa_same_pad_left), e = the positions next to a cut that differ,
+        at the current rate (e = 0 for the samples):
+          strided Conv1D (stride s, K taps, left pad pl): output o reads inputs o s - pl .. o s - pl + K - 1, so the
+            first ceil((e + pl) / s) and the last floor((e + K - 1 - pl) / s) outputs differ: e <- the larger,
+            hop <- s hop (the `down` convs);
+          Conv1D (stride 1, K taps, dilation d): e <- e + max(pl, (K - 1) d - pl) (conv_a and conv_b of every
+            residual block — the skip path adds nothing — and proj).
+        The pads of the strided convs do not depend on the length only when every stage length is a multiple of its
+        stride (the pad is then K - s in all): that is why the lengths must be multiples of hop, under which a chunk
+        that starts at a multiple of hop also keeps every stage's phase."""
+        e, hop = 0, 1
+        T = 1
+        for blk in self.blocks:
+            T *= blk.stride ** blk.down_depth
+        T <<= 10  # any multiple of the hop: the pads below are those of every such length
+
+        def conv(c, e):
+            assert c.s == 1, f"{c.name}: only the down convs of the encoder are strided"
+            pl = V.same_pad_left(T, c.K, 1, c.d)
+            return e + max(pl, (c.K - 1) * c.d - pl)
+
+        t = T
+        for blk in self.blocks:
+            for down, res in zip(blk.down, blk.res):
+                assert down.d == 1 and t % down.s == 0
+                pl = V.same_pad_left(t, down.K, down.s, 1)
+                e = max(-(-(e + pl) // down.s), (e + down.K - 1 - pl) // down.s)
+                hop *= down.s
+                t //= down.s
+                for rb in res.blocks:
+                    e = conv(rb.conv_b, conv(rb.conv_a, e))
+            e = conv(blk.proj, e)
+        return e, hop
+
 
 class Decoder(Layer):
     def __init__(self, output_dim, embed_width, residual_width, residual_depth, depth, down_depth, strides,

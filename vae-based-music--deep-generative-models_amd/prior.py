@@ -32,6 +32,7 @@ import torch
 
 import vqa_dp
 import vqa_lib as V
+from code_feed import CodeFeed
 from conditioners import ConditionerNet
 from vqa_layers import CKPT_VERSION, ParamStore, checkpoint_layout
 from vqa_metrics import Mean
@@ -553,7 +554,8 @@ class FMHABasedAutoregressiveModel:
 class Prior:
     """prior.py:102-372: trains one level's FMHABasedAutoregressiveModel on the VQ-VAE's codes.
 
-    train_step(x) takes raw audio (N, T, 1) (encoded with `vqvae_model`) or the codes themselves (N, T_l) int64.
+    train_step(x) takes raw audio (N, T, 1) (encoded with `vqvae_model`), the codes themselves (N, T_l) int64, or
+    a code_feed.CodeFeed over a device-resident corpus of codes tokenized once (its next batch; no copy).
     Returns {"loss", "perplexity(per word)", "accuracy"} running means (device tensors)."""
 
     def __init__(self, level, z_shapes, bins, down_depth, strides, vqvae_model, prior_kwargs, x_cond_kwargs,
@@ -588,6 +590,7 @@ class Prior:
         self.teacher_seed = 3
         self._step = 0
         self._graph = None
+        self._graph_feed = None  # the CodeFeed a captured step draws from (None: it copies the caller's codes in)
 
     @property
     def metrics(self):
@@ -601,6 +604,7 @@ class Prior:
         self.optimizer = optimizer or Adam()
         self.optimizer.build(self.prior.store)
         self._graph = None
+        self._graph_feed = None
 
     def reset_metrics(self):
         for m in self.metrics:
@@ -623,7 +627,12 @@ class Prior:
         x is raw audio (N, T, 1) (encoded with `vqvae_model`: this level's codes and, for the upsampler
         conditioning, the level above's, prior.py:257-260) or the codes themselves (int64). A tuple carries the
         extras: (audio, y) as the reference's train_step takes it (prior.py:251-254), (codes, upper_codes) for a
-        prior conditioned on the level above, (codes, y) / (codes, upper_codes, y) with genre labels."""
+        prior conditioned on the level above, (codes, y) / (codes, upper_codes, y) with genre labels. A
+        code_feed.CodeFeed gives its next batch: the feed's own buffers, used as they are."""
+        if isinstance(x, CodeFeed):
+            self._check_feed(x)
+            x.next()
+            return self._feed_inputs(x)
         extras = []
         if isinstance(x, (tuple, list)):
             x, extras = x[0], list(x[1:])
@@ -647,6 +656,23 @@ class Prior:
             if y.numel() != codes.shape[0]:
                 raise ValueError(f"{y.numel()} labels for {codes.shape[0]} sequences")
         return codes, upper, y
+
+    def _check_feed(self, feed: CodeFeed):
+        """ValueError unless the feed's batches fit this prior; settled on the host before anything is launched."""
+        if self.prior.conditioner is not None and feed.upper is None:
+            raise ValueError("a conditioned prior needs a feed with the level above's codes (CodeFeed(conditioned=True))")
+        if feed.n_ctx != self.context_length:
+            raise ValueError(f"the feed's n_ctx {feed.n_ctx} is not the prior's context length {self.context_length}")
+        if feed.y is not None and self.label_conditioner is None:
+            raise ValueError("the feed has labels and the prior was built without genre_classes")
+        if feed.corpus.num_embeddings > self.bins:
+            raise ValueError(f"the corpus holds codes below {feed.corpus.num_embeddings}, the prior has {self.bins} bins")
+        if feed.codes.device.type != self.device.type:
+            raise ValueError(f"the feed's buffers are on {feed.codes.device}, the prior on {self.device}")
+
+    def _feed_inputs(self, feed: CodeFeed):
+        """The feed's buffers as (codes, upper, y); a prior without a conditioner leaves the level above unused."""
+        return feed.codes, (feed.upper if self.prior.conditioner is not None else None), feed.y
 
     def results(self):
         loss = self.train_loss_tracker.result()
@@ -753,27 +779,40 @@ class Prior:
 
     def train_step(self, x, teacher_force_rate=0.2, tf_mask=None):
         """prior.py:241-335. tf_mask (N, T) bool overrides the random teacher-forcing draw (parity tests)."""
-        codes, upper, y = self._codes(x)
         # the captured graph bakes in its teacher-forcing rate: another rate (e.g. a schedule) runs eagerly
-        if (self._graph is not None and tf_mask is None and self._graph_fits(codes, upper, y)
-                and float(teacher_force_rate) == self._graph_rate):
+        replayable = (self._graph is not None and tf_mask is None
+                      and float(teacher_force_rate) == self._graph_rate)
+        if replayable and self._graph_feed is not None:
+            # the step captured with this very feed draws its batch inside the graph; any other feed (or the same
+            # one after a change of seed, which the graph's launch does not see) and tensors run eagerly below —
+            # the graph's inputs are the feed's buffers, which a replay overwrites
+            if x is self._graph_feed and x.seed == self._graph_feed_seed:
+                self._check_feed(x)
+                self._replay()
+                return self.results()
+            replayable = False
+        codes, upper, y = self._codes(x)
+        if replayable and self._graph_fits(codes, upper, y):
             self._graph_in[0].copy_(codes)
             if upper is not None:
                 self._graph_in[1].copy_(upper)
             if y is not None:
                 self._graph_in[2].copy_(y)
-            g1, g2 = self._graph
-            g1.replay()
-            if g2 is not None:
-                self._exchange()
-                g2.replay()
-            self._step += 1
+            self._replay()
             return self.results()
         self._compute(codes, upper, teacher_force_rate, tf_mask, y)
         self._exchange()
         self._apply()
         self._step += 1
         return self.results()
+
+    def _replay(self):
+        g1, g2 = self._graph
+        g1.replay()
+        if g2 is not None:
+            self._exchange()
+            g2.replay()
+        self._step += 1
 
     def _graph_fits(self, codes, upper, y):
         c, u, l = self._graph_in
@@ -813,22 +852,38 @@ class Prior:
         """Record the whole step (both passes, the conditioner, backward, Adam, metrics) as one hipGraph — two
         around the eager all_reduce under data parallelism; later train_step calls with the same shapes copy the
         codes (upper-level codes, labels) in and replay (the teacher-forcing draw and dropout advance on the
-        device)."""
-        codes, upper, y = self._codes(codes_example)
-        self._graph_in = tuple(None if t is None else t.clone() for t in (codes, upper, y))
+        device).
+        codes_example may be a code_feed.CodeFeed: its gather launch and counter increment are then recorded at the
+        head of the first graph and the graph's inputs are the feed's own buffers (no copy); the warm-up steps are
+        real steps on the feed's next batches, and a later train_step(feed) with this feed replays."""
+        feed = codes_example if isinstance(codes_example, CodeFeed) else None
+        self._graph = None
+        if feed is not None:
+            self._check_feed(feed)
+            self._graph_in = self._feed_inputs(feed)
+        else:
+            codes, upper, y = self._codes(codes_example)
+            self._graph_in = tuple(None if t is None else t.clone() for t in (codes, upper, y))
+        self._graph_feed, self._graph_feed_seed = feed, (feed.seed if feed is not None else None)
         c, u, l = self._graph_in
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
             for _ in range(warmup):
+                if feed is not None:
+                    feed.next()
                 self._compute(c, u, teacher_force_rate, None, l)
                 self._exchange()
                 self._apply()
+                if feed is not None:
+                    self._step += 1
         torch.cuda.current_stream(self.device).wait_stream(s)
         torch.cuda.synchronize(self.device)
         pool = torch.cuda.graph_pool_handle()
         g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1, pool=pool, capture_error_mode="thread_local"):
+            if feed is not None:
+                feed.next()
             self._compute(c, u, teacher_force_rate, None, l)
             if not vqa_dp.active(self.process_group):
                 self._apply()
@@ -840,6 +895,23 @@ class Prior:
         self._graph = (g1, g2)
         self._graph_rate = float(teacher_force_rate)
         torch.cuda.synchronize(self.device)
+
+    def fit(self, x, epochs=1, teacher_force_rate=0.2, verbose=0):
+        """Minimal keras fit over a code_feed.CodeFeed: the trackers reset per epoch (keras semantics), an epoch is
+        the feed's steps_per_epoch steps (graph replays once the step is captured with that feed); batch size,
+        shuffling and seed are the feed's. Returns the history of epoch-end results."""
+        if not isinstance(x, CodeFeed):
+            raise ValueError("Prior.fit trains from a code_feed.CodeFeed")
+        self._check_feed(x)
+        hist = []
+        for ep in range(epochs):
+            self.reset_metrics()
+            for _ in range(x.steps_per_epoch):
+                self.train_step(x, teacher_force_rate=teacher_force_rate)
+            hist.append({k: float(v) for k, v in self.results().items()})
+            if verbose:
+                print(f"epoch {ep + 1}/{epochs}", hist[-1])
+        return hist
 
     # -------------------------------------------------------------- checkpoint
     def save(self, path: str):

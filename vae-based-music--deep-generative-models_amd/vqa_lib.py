@@ -43,7 +43,7 @@ EXPORTED = [
     "vqa_axpy", "vqa_dropout", "vqa_scale_f32", "vqa_tf_mix", "vqa_attn_fwd", "vqa_attn_bwd", "vqa_head_wt",
     "vqa_head_fwd", "vqa_head_bwd_workspace", "vqa_head_bwd", "vqa_rowsum_workspace", "vqa_rowsum", "vqa_prior_decode_cache_bytes",
     "vqa_prior_decode", "vqa_prior_decode_primed",
-    "vqa_corpus_steps_per_epoch", "vqa_corpus_batch", "vqa_pcm_encode",
+    "vqa_corpus_steps_per_epoch", "vqa_corpus_batch", "vqa_pcm_encode", "vqa_code_batch",
 ]
 
 
@@ -148,6 +148,7 @@ _SIGS = {
     # device-resident corpus feed
     "vqa_corpus_steps_per_epoch": (_L, [_L, _I, _I]),
     "vqa_corpus_batch": (_I, [_P, _L, _I, _P, _P, _L, _P, _P, _P, _I, _L, _U, _P, _L, _I, _I, _I, _P]),
+    "vqa_code_batch": (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _L, _P, _P, _P, _P, _I, _L, _U, _P, _L, _I, _I, _I, _P]),
     # waveform -> int16 PCM
     "vqa_pcm_encode": (_I, [_P, _L, _P, _L, _I, _L, _L, _L, _F, _P, _P]),
 }
@@ -574,6 +575,45 @@ def corpus_batch(corpus, corpus_len, starts, labels, x, labels_out=None, index_o
     _check(lib().vqa_corpus_batch(ptr(corpus), corpus_len, pcm, ptr(starts), ptr(labels), M, ptr(x), ptr(labels_out),
                                   ptr(index_out), B, T, int(seed), ptr(counter), int(step), int(rank), int(world),
                                   int(bool(shuffle)), stream()), "vqa_corpus_batch")
+
+
+CODE_I16, CODE_I32 = 0, 1  # VQA_CODE_*
+
+
+def code_batch(codes, codes_len, starts, labels, z, upper=None, upper_len=0, rate=1, z_upper=None, labels_out=None,
+               index_out=None, seed=0, counter=None, step=0, rank=0, world=1, shuffle=True):
+    """One step's batch of a device-resident code corpus (vqa_code_batch, include/vqa.h): codes (and upper, the level
+    above's codes of the same tracks) are 1-D int16 or int32 tensors allocated up to a multiple of 16 bytes past
+    codes_len (upper_len) codes, starts / labels the (M,) int64 window table, z the (B, T) int64 batch, z_upper the
+    (B, T / rate) int64 windows of the level above; labels_out / index_out (B,) int64."""
+    if codes.dtype == torch.int16:
+        width = CODE_I16
+    elif codes.dtype == torch.int32:
+        width = CODE_I32
+    else:
+        raise VQAError(f"code_batch: the codes are int16 or int32 (got {codes.dtype})")
+    if upper is not None and upper.dtype != codes.dtype:
+        raise VQAError(f"code_batch: upper is {upper.dtype}, codes {codes.dtype}")
+    if starts.dtype != torch.int64 or any(t is not None and t.dtype != torch.int64
+                                         for t in (z, z_upper, labels, labels_out, index_out, counter)):
+        raise VQAError("code_batch: starts, labels, z, z_upper, labels_out, index_out and counter are int64")
+    codes_len, upper_len, rate = int(codes_len), int(upper_len), int(rate)
+    for t, n, what in ((codes, codes_len, "codes"), (upper, upper_len, "upper")):
+        if t is not None and (n * t.element_size() + 15) // 16 * 16 > t.numel() * t.element_size():
+            raise VQAError(f"code_batch: the {what} tensor ({t.numel()} codes) does not cover its length {n} "
+                           f"rounded up to 16 bytes")
+    M = starts.numel()
+    if labels is not None and labels.numel() != M:
+        raise VQAError(f"code_batch: {labels.numel()} labels for {M} windows")
+    B, T = z.shape[0], z.numel() // z.shape[0]
+    if z_upper is not None and rate >= 1 and z_upper.numel() != B * (T // rate):
+        raise VQAError(f"code_batch: z_upper holds {z_upper.numel()} codes, not {B} x {T // rate}")
+    for t in (labels_out, index_out):
+        if t is not None and t.numel() != B:
+            raise VQAError(f"code_batch: labels_out / index_out hold {B} entries")
+    _check(lib().vqa_code_batch(ptr(codes), codes_len, ptr(upper), upper_len, rate, width, ptr(starts), ptr(labels), M,
+                                ptr(z), ptr(z_upper), ptr(labels_out), ptr(index_out), B, T, int(seed), ptr(counter),
+                                int(step), int(rank), int(world), int(bool(shuffle)), stream()), "vqa_code_batch")
 
 
 def pcm_encode(x, out, x0=0, o0=0, n=None, gain=1.0, clipped=None):

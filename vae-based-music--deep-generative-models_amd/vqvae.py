@@ -135,6 +135,34 @@ def decode_plan(total_codes, chunk_codes, halo):
             for lo in range(0, total, chunk)]
 
 
+def encode_halo_for(level, down_depth, strides, residual_width=64, residual_depth=4, dilation_factor=1, latent_dim=64,
+                    channels=1) -> int:
+    """VQVAE.encode_halo(level) of a model with this configuration, from the layer list alone (built on the host
+    with no weights: needs no GPU)."""
+    enc = Encoder(output_dim=latent_dim, residual_width=residual_width, residual_depth=residual_depth,
+                  depth=level + 1, down_depth=list(down_depth)[:level + 1], strides=list(strides)[:level + 1],
+                  dilation_factor=dilation_factor)
+    enc.build(ParamStore(), f"enc{level}", channels, torch.float32)
+    return enc.receptive_reach()[0]
+
+
+def encode_plan(total_samples, chunk_samples, halo_codes, hop):
+    """The chunks of a bounded-memory encode of `total_samples` samples: a list of (in_lo, in_hi, core_lo, core_hi)
+    in samples, every value a multiple of `hop` (the samples per code). The cores [core_lo, core_hi) are consecutive
+    ranges of at most chunk_samples samples that tile [0, total_samples) exactly once; [in_lo, in_hi) is the core
+    widened by halo_codes * hop samples on each side and clamped to the sequence, so a true end of the sequence is
+    reached by the chunk itself and gets the encoder's own zero padding, as in a whole-sequence encode. total_samples
+    and chunk_samples must be multiples of hop (Encoder.receptive_reach holds for such lengths only)."""
+    total, chunk, halo, hop = int(total_samples), int(chunk_samples), int(halo_codes), int(hop)
+    if total <= 0 or chunk <= 0 or hop <= 0:
+        raise ValueError(f"encode_plan: total_samples {total}, chunk_samples {chunk} and hop {hop} must be positive")
+    if halo < 0:
+        raise ValueError(f"encode_plan: negative halo {halo}")
+    if total % hop or chunk % hop:
+        raise ValueError(f"encode_plan: total_samples {total} and chunk_samples {chunk} must be multiples of hop {hop}")
+    return decode_plan(total, chunk, halo * hop)
+
+
 class VQVAE:
     def __init__(self, input_shape, levels, latent_dim, down_depth, strides, num_embeddings=128, residual_width=64,
                  residual_depth=4, dilation_factor=1, train_variance=1.0, *, dtype="bf16", device="cuda",
@@ -595,6 +623,45 @@ class VQVAE:
     def encode(self, x, start_level=0, end_level=None):
         end_level = self.levels if end_level is None else end_level
         return [self.encode_level(x, l) for l in range(start_level, end_level)]
+
+    # ------------------------------------------------------------------ bounded-memory encode
+    def encode_halo(self, level) -> int:
+        """Codes on each side of a core range of level `level` whose samples influence that core's codes (an upper
+        bound, derived from the level's encoder layers: Encoder.receptive_reach)."""
+        return self.encoders[level].receptive_reach()[0]
+
+    @property
+    def encode_hops(self) -> List[int]:
+        """Audio samples per code of every level's encoder (8 / 32 / 128 at down_depth [3, 2, 2])."""
+        return [self.encoders[l].receptive_reach()[1] for l in range(self.levels)]
+
+    def encode_chunked(self, x, level, chunk_samples=1 << 18):
+        """encode_level(x, level) with bounded memory, for a sequence of any length that is a multiple of the
+        level's hop: x (B, T, 1) fp32 -> (B, T / hop) int64 codes, equal to the whole-sequence encode. The sequence
+        is encoded in cores of chunk_samples samples (rounded down to a multiple of hop, at least one code), each
+        from its samples widened by encode_halo(level) codes' worth on both sides (encode_plan); Encoder.forward
+        runs with nothing saved and only the core's codes are kept, so one chunk's activations are alive at a
+        time."""
+        x = torch.as_tensor(x)
+        if x.dim() == 2:
+            x = x.unsqueeze(-1)
+        if x.dim() != 3 or x.shape[-1] != self.channels or x.shape[0] < 1:
+            raise ValueError(f"encode_chunked: x must be (B, T, {self.channels}) (got shape {tuple(x.shape)})")
+        x = x.to(device=self.device, dtype=torch.float32)
+        enc, vq = self.encoders[level], self.vqs[level]
+        halo, hop = enc.receptive_reach()
+        B, T = x.shape[0], x.shape[1]
+        if T < hop or T % hop:
+            raise ValueError(f"encode_chunked: length {T} is not a positive multiple of level {level}'s hop {hop}")
+        chunk = max(int(chunk_samples) // hop, 1) * hop if int(chunk_samples) > 0 else 0
+        out = torch.empty(B, T // hop, dtype=torch.int64, device=self.device)
+        with torch.no_grad():
+            for in_lo, in_hi, core_lo, core_hi in encode_plan(T, chunk, halo, hop):
+                z = enc.forward(x[:, in_lo:in_hi].contiguous())
+                idx = vq.get_code_indices(z.reshape(-1, self.latent_dim)).view(B, (in_hi - in_lo) // hop)
+                out[:, core_lo // hop:core_hi // hop] = idx[:, (core_lo - in_lo) // hop:(core_hi - in_lo) // hop]
+                del z, idx
+        return out
 
     def decode_level(self, zq, level, chunk=1):
         """vqvae.py:238-251: one_hot(zq) @ E^T (a row gather of ET) -> decoder."""
