@@ -380,6 +380,31 @@ int vqa_code_batch(const void* codes, int64_t codes_len, const void* upper /* ma
 int vqa_pcm_encode(const float* x, int64_t ldx, int16_t* out, int64_t ldo, int B, int64_t x0, int64_t o0, int64_t n,
                    float gain, int32_t* clipped /* may be NULL */, vqa_stream_t stream);
 
+/* Polyphase sample-rate conversion by up / down (coprime: L = sr_out / g, M = sr_in / g, g = gcd of the rates) with
+ * a caller-supplied fp32 tap table `taps` (up, taps_per_phase), row-major. With P = taps_per_phase and W = P / 2,
+ * output m of a track of track_len samples sits at input time m * M / L exactly (no delay):
+ *   k0, r = divmod(m * M, L)  (int64),   y[m] = sum_{i = 0}^{P-1} x[k0 + i - W + 1] * taps[r][i]
+ * with x[k] = 0 outside [0, track_len); the track has ceil(track_len * L / M) outputs. The P products of an output
+ * are accumulated in fp32 in ascending i, one fused multiply-add each: the bits of y[m] depend on r, P and the
+ * inputs only, never on m0, the tile or B, so a track converted in chunks equals the track converted whole.
+ * Row b of x (x_dtype 0: fp32, 1: int16 read as x * 2^-15; ldx samples between rows) holds samples
+ * [in0, in0 + n_in) of its track; the call writes outputs m in [m0, m0 + n_out) to out[b * ldo + (m - m0)].
+ * in0 = m0 = 0, n_in = track_len, n_out = ceil(track_len * L / M) converts the whole track; other values convert
+ * one chunk of a streamed track. Only those n_in samples of a row are read and those n_out outputs written.
+ * A workgroup computes a tile of consecutive outputs of one row from an LDS copy of the input span it needs; the
+ * tap table is staged in LDS too when table and span fit 160 KiB, and read from global memory otherwise
+ * (vqa_resample_route reports which, and the tile size, from the function the launcher uses; host only, no GPU).
+ * VQA_E_INVALID_ARG before any launch (messages start "resample:"): a null x, out or taps; B outside [1, 65535];
+ * up or down < 1 or not coprime; taps_per_phase odd or outside [2, 8192]; an unknown x_dtype; x not aligned to its
+ * element, out or taps not 4-byte aligned; n_out or track_len not positive; a negative m0, in0 or n_in;
+ * m0 + n_out > ceil(track_len * L / M); ldx < n_in or ldo < n_out; (m0 + n_out) * down beyond int64; the input span
+ * the outputs need, [floor(m0 M / L) - W + 1, floor((m0 + n_out - 1) M / L) + W] clipped to [0, track_len), not
+ * inside [in0, in0 + n_in). */
+int vqa_resample(const void* x, int x_dtype, int64_t ldx, int64_t in0, int64_t n_in, int64_t track_len, float* out,
+                 int64_t ldo, int64_t m0, int64_t n_out, int B, int up, int down, const float* taps,
+                 int taps_per_phase, vqa_stream_t stream);
+int vqa_resample_route(int up, int down, int taps_per_phase, int* table_in_lds, int* tile_outputs);
+
 /* ---- multi-resolution spectral loss --------------------------------------------------------------
  * Replaces vqvae.py:309-326 (_multispectral_loss) over data_utils.py:25-30 (spectral = |tf.signal.stft|)
  * and data_utils.py:33-40 (norm = tf.norm 'fro'), plus its GradientTape backward (vqvae.py:143):

@@ -8,6 +8,8 @@ lives on the device. The launch is therefore the same every step: `VQVAE.capture
 the step's hipGraph and an epoch of training is nothing but graph replays, with no host batch and no copy.
 
   corpus = AudioCorpus.from_files(files, labels, sr=22050, window=65536)     # or from_arrays(tracks, labels, ...)
+  corpus = AudioCorpus.from_files(files, labels, sr=3000, window=8192, resample="best")  # files of any rate, converted
+                                                                             # to sr on the device (resample.Resampler)
   train, val = corpus.split(0.1, seed=42)
   feed = AudioFeed(train, batch_size=32, seed=1)
   model.capture_train_step(feed); model.fit(feed, epochs=10); model.evaluate(AudioFeed(val, 32, shuffle=False))
@@ -22,6 +24,7 @@ import torch
 import vqa_dp
 import vqa_lib as V
 from data_utils import read_wav_pcm, stratified_split
+from resample import Resampler, design
 
 
 def window_starts(track_lengths: Sequence[int], window: int, hop: Optional[int] = None,
@@ -95,10 +98,16 @@ class AudioCorpus:
 
     @classmethod
     def from_arrays(cls, tracks, labels=None, window: int = 65536, hop: Optional[int] = None, device="cuda",
-                    max_signal_len: Optional[int] = None) -> "AudioCorpus":
+                    max_signal_len: Optional[int] = None, rates: Optional[Sequence[int]] = None,
+                    sr: Optional[int] = None, resample: Optional[str] = None) -> "AudioCorpus":
         """tracks: a list of 1-D arrays (or (1, n) / (n, 1): one channel), one per track; labels: one class per
         track. Tracks that are ALL int16 are stored as int16 (the kernel scales by 2^-15); otherwise the whole corpus
-        is float32 (an int16 track among them scaled by 2^-15, so both forms feed the same values)."""
+        is float32 (an int16 track among them scaled by 2^-15, so both forms feed the same values).
+        rates (one per track) with sr: the tracks' own sample rates and the corpus's. By default a track of another
+        rate is a ValueError; resample="best" / "fast" converts it to sr on the device (resample.Resampler: an int16
+        track is uploaded as int16, the result written straight into the corpus), tracks already at sr are not
+        touched, and the corpus is float32 as soon as one track is converted. window, hop and max_signal_len count
+        samples at sr."""
         arrs = []
         for t in tracks:
             a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
@@ -111,6 +120,16 @@ class AudioCorpus:
             raise ValueError("no tracks")
         if labels is not None and len(labels) != len(arrs):
             raise ValueError(f"{len(labels)} labels for {len(arrs)} tracks")
+        if rates is not None:
+            if sr is None or len(rates) != len(arrs):
+                raise ValueError(f"rates needs sr and one rate per track ({len(rates)} rates, {len(arrs)} tracks)")
+            other = [j for j, r in enumerate(rates) if int(r) != int(sr)]
+            if other and resample is None:
+                raise ValueError(f"track {other[0]}: sample rate {int(rates[other[0]])} Hz, requested {int(sr)} Hz "
+                                 f"(tracks are not resampled)")
+            if other:
+                return cls._from_arrays_resampled(arrs, [int(r) for r in rates], int(sr), resample, labels, window,
+                                                  hop, device, max_signal_len)
         if all(a.dtype == np.int16 for a in arrs):
             dt = np.int16
         else:
@@ -126,20 +145,51 @@ class AudioCorpus:
                    lengths, tl)
 
     @classmethod
+    def _from_arrays_resampled(cls, arrs, rates, sr, quality, labels, window, hop, device, max_signal_len):
+        """from_arrays when a track has another rate than sr: the float32 corpus is assembled on the device, every
+        track of another rate converted by the resampling kernel into its place."""
+        design(rates[0], sr, quality)  # an unknown quality is refused before anything is uploaded
+        lengths = np.array([len(a) if r == sr else design(r, sr, quality).output_length(len(a))
+                            for a, r in zip(arrs, rates)], np.int64)
+        n = int(lengths.sum())
+        samples = torch.zeros(_padded_len(n, 4), dtype=torch.float32, device=device)
+        off = 0
+        for a, r, m in zip(arrs, rates, lengths):
+            m = int(m)
+            if r == sr:
+                h = a.astype(np.float32) / 32768.0 if a.dtype == np.int16 else a.astype(np.float32)
+                samples[off:off + m] = torch.from_numpy(np.array(h)).to(device)  # a copy: a file's frames are read-only
+            elif m:
+                h = a if a.dtype == np.int16 else a.astype(np.float32)
+                Resampler(r, sr, quality, device)(torch.from_numpy(np.array(h)).to(device), out=samples[off:off + m])
+            off += m
+        starts, track = window_starts(lengths, window, hop, max_signal_len)
+        tl = None if labels is None else np.asarray(labels, np.int64)
+        return cls(samples, n, window, starts, None if tl is None else tl[track], track, lengths, tl)
+
+    @classmethod
     def from_files(cls, files, labels=None, sr: int = 22050, window: int = 65536, hop: Optional[int] = None,
                    duration: Optional[float] = None, max_signal_len: Optional[int] = None,
-                   device="cuda") -> "AudioCorpus":
-        """Integer-PCM WAV files of rate `sr` (data_utils.read_wav_pcm; no resampling), `duration` seconds of each
-        at most, as split_convert loads them. 16-bit mono files stay int16 end to end (never through float); a file
-        with more channels is averaged to mono and, like any other bit depth, makes the corpus float32."""
-        tracks = []
+                   device="cuda", resample: Optional[str] = None) -> "AudioCorpus":
+        """Integer-PCM WAV files of rate `sr` (data_utils.read_wav_pcm; by default no resampling), `duration`
+        seconds of each at most, as split_convert loads them. 16-bit mono files stay int16 end to end (never through
+        float); a file with more channels is averaged to mono and, like any other bit depth, makes the corpus
+        float32. resample="best" / "fast" reads every file at its own rate (`duration` stays seconds of the file)
+        and converts those of another rate to sr on the device (from_arrays with rates): a 16-bit mono file is
+        uploaded as int16, the others as their fp32 mono average."""
+        tracks, rates = [], []
         for f in files:
-            a, bits, _ = read_wav_pcm(f, sr=sr, duration=duration)
+            a, bits, rate = read_wav_pcm(f, sr=sr if resample is None else None, duration=duration)
+            rates.append(rate)
             if bits == 16 and a.shape[1] == 1:
                 tracks.append(a[:, 0])
             else:
                 tracks.append((a.astype(np.float64) / float(1 << (bits - 1))).mean(axis=1).astype(np.float32))
-        return cls.from_arrays(tracks, labels, window=window, hop=hop, device=device, max_signal_len=max_signal_len)
+        if resample is None:
+            return cls.from_arrays(tracks, labels, window=window, hop=hop, device=device,
+                                   max_signal_len=max_signal_len)
+        return cls.from_arrays(tracks, labels, window=window, hop=hop, device=device, max_signal_len=max_signal_len,
+                               rates=rates, sr=sr, resample=resample)
 
     def subset(self, tracks: Sequence[int]) -> "AudioCorpus":
         """The corpus of the windows of the given tracks; the sample tensor is shared, not copied."""

@@ -10,8 +10,9 @@ zero-padded at the end to n_fft).
 
 data_utils.py:43-238  load_audio, splitsongs, split_convert, read_data, generate_genre_samples: a folder of
 genre-labelled WAVs turned into training windows and labels, with the reference's names, arguments and result
-shapes. Files are integer-PCM WAV read with the standard library (no librosa: nothing is resampled, a file whose
-rate is not the requested one is an error) and the stratified split is a deterministic one of our own (no sklearn).
+shapes. Files are integer-PCM WAV read with the standard library (no librosa: by default nothing is resampled and a
+file whose rate is not the requested one is an error; resample="best" / "fast" converts it with the polyphase filter
+of resample.py) and the stratified split is a deterministic one of our own (no sklearn).
 These build host arrays, as the reference does; training itself reads a device-resident corpus through
 audio_feed.AudioCorpus / AudioFeed (one gather kernel per step inside the step's graph).
 
@@ -27,6 +28,7 @@ import numpy as np
 import torch
 
 import vqa_lib as V
+from resample import design, resample_reference
 
 STFT_ARGS = [(2048, 1024, 512),  # n_fft
              (240, 120, 50),  # hop_length
@@ -202,13 +204,18 @@ def save_wavs(pcm, directory, sr, labels=None, prefix="sample"):
     return paths
 
 
-def load_audio(file, sr=22050, offset=0.0, duration=None, mono=False):
+def load_audio(file, sr=22050, offset=0.0, duration=None, mono=False, resample=None):
     """data_utils.py:43-48 (librosa.load there): -> (C, n) float32, a sample being int / 2^(bits-1) (8-bit data is
     unsigned with a 128 offset), exactly for up to 24 bits. Integer-PCM WAV of 8, 16, 24 or 32 bits through the
-    standard library's `wave`; `mono` averages the channels; `offset` / `duration` are seconds. There is no
-    resampling: a file whose rate is not `sr` raises ValueError (naming both rates), as does a non-PCM WAV."""
-    a, bits, _ = read_wav_pcm(file, sr=sr, offset=offset, duration=duration)
+    standard library's `wave`; `mono` averages the channels; `offset` / `duration` are seconds. By default there is
+    no resampling: a file whose rate is not `sr` raises ValueError (naming both rates), as does a non-PCM WAV.
+    resample="best" / "fast" reads the file at its own rate (`offset` / `duration` stay seconds of the file) and
+    converts every channel to `sr` on the host (resample.resample_reference, fp64) before `mono`:
+    -> (C, ceil(n * L / M)); a file already at `sr` is returned as without it."""
+    a, bits, rate = read_wav_pcm(file, sr=sr if resample is None else None, offset=offset, duration=duration)
     x = (a.astype(np.float64) / float(1 << (bits - 1))).T  # (C, n)
+    if resample is not None:
+        x = resample_reference(x, design(rate, sr, resample))
     if mono:
         x = x.mean(axis=0, keepdims=True)
     return np.ascontiguousarray(x, dtype=np.float32)
@@ -236,14 +243,15 @@ def stratified_split(labels, test_fraction, seed=42):
     return train, test
 
 
-def split_convert(X, y, sample_rate=3000, duration=30, max_signal_len=660000, split_window=1.0, split_overlap=0.0):
+def split_convert(X, y, sample_rate=3000, duration=30, max_signal_len=660000, split_window=1.0, split_overlap=0.0,
+                  resample=None):
     """data_utils.py:100-136: every file of X loaded (load_audio, `duration` seconds, cut to max_signal_len
     samples) and cut by splitsongs -> (waves (n, C, chunk) float32, genres (n,), file labels (n,) — the file's
-    base name repeated for each of its chunks)."""
+    base name repeated for each of its chunks). `resample` is load_audio's."""
     arr_waves, arr_genres, arr_file_label = [], [], []
     for fn, genre in zip(X, y):
         file_label = str(fn).split('/')[-1]
-        signal = load_audio(fn, sr=sample_rate, duration=duration)[:, :max_signal_len]
+        signal = load_audio(fn, sr=sample_rate, duration=duration, resample=resample)[:, :max_signal_len]
         signals, ys = splitsongs(signal, genre, window=split_window, overlap=split_overlap)
         arr_waves.extend(signals)
         arr_genres.extend(ys)
@@ -270,15 +278,15 @@ def list_genre_files(src_dir, genres, max_files_per_genre=1000):
 
 def read_data(src_dir, genres, test_data_percentage=0.1, sample_rate=22050, duration=30, split_window=1.0,
               split_overlap=0.0, max_signal_len=660000, shuffle_after_split=False, max_files_per_genre=1000,
-              random_state=42):
+              random_state=42, resample=None):
     """data_utils.py:146-206 -> (X_train, y_train, y_file_train, X_test, y_test, y_file_test), X (n, C, chunk)
     float32. The files are split into train and test stratified by genre and each side is then loaded and cut
     (split_convert); with shuffle_after_split all files are cut first and the chunks are split stratified by file.
     The split is stratified_split with `random_state` as its seed (the reference's 42): deterministic, but not
-    sklearn's partition."""
+    sklearn's partition. `resample` is load_audio's (None: files of another rate are an error)."""
     arr_fn, arr_genres = list_genre_files(src_dir, genres, max_files_per_genre)
     kw = dict(sample_rate=sample_rate, duration=duration, max_signal_len=max_signal_len, split_window=split_window,
-              split_overlap=split_overlap)
+              split_overlap=split_overlap, resample=resample)
     if shuffle_after_split:
         X, y, y_file = split_convert(arr_fn, arr_genres, **kw)
         tr, te = stratified_split(y_file, test_data_percentage, random_state)

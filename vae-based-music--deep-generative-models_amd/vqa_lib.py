@@ -44,6 +44,7 @@ EXPORTED = [
     "vqa_head_fwd", "vqa_head_bwd_workspace", "vqa_head_bwd", "vqa_rowsum_workspace", "vqa_rowsum", "vqa_prior_decode_cache_bytes",
     "vqa_prior_decode", "vqa_prior_decode_primed",
     "vqa_corpus_steps_per_epoch", "vqa_corpus_batch", "vqa_pcm_encode", "vqa_code_batch",
+    "vqa_resample", "vqa_resample_route",
 ]
 
 
@@ -151,6 +152,9 @@ _SIGS = {
     "vqa_code_batch": (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _L, _P, _P, _P, _P, _I, _L, _U, _P, _L, _I, _I, _I, _P]),
     # waveform -> int16 PCM
     "vqa_pcm_encode": (_I, [_P, _L, _P, _L, _I, _L, _L, _L, _F, _P, _P]),
+    # polyphase sample-rate conversion
+    "vqa_resample": (_I, [_P, _I, _L, _L, _L, _L, _P, _L, _L, _L, _I, _I, _I, _P, _I, _P]),
+    "vqa_resample_route": (_I, [_I, _I, _I, _P, _P]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -634,6 +638,57 @@ def pcm_encode(x, out, x0=0, o0=0, n=None, gain=1.0, clipped=None):
     n = ldx - int(x0) if n is None else int(n)
     _check(lib().vqa_pcm_encode(ptr(x), ldx, ptr(out), ldo, B, int(x0), int(o0), n, float(gain), ptr(clipped),
                                 stream()), "vqa_pcm_encode")
+
+
+RESAMPLE_F32, RESAMPLE_I16 = 0, 1  # x_dtype of vqa_resample
+
+
+def _rows(t, what):
+    """(pointer, rows, samples per row, samples between rows) of a device tensor (n,) or (B, n) whose rows are
+    dense; the rows may be a slice of wider ones (a view: stride(0) is what the kernel steps by)."""
+    if not t.is_cuda:
+        raise VQAError(f"resample: {what} is a device tensor (got a CPU tensor)")
+    if t.dim() not in (1, 2) or t.numel() == 0 or t.stride(-1) != 1:
+        raise VQAError(f"resample: {what} is (n,) or (B, n) with dense rows (got shape {tuple(t.shape)}, strides "
+                       f"{t.stride()})")
+    B = t.shape[0] if t.dim() == 2 else 1
+    ld = t.stride(0) if t.dim() == 2 and B > 1 else t.shape[-1]
+    if ld < t.shape[-1]:
+        raise VQAError(f"resample: the rows of {what} overlap (strides {t.stride()})")
+    return ctypes.c_void_p(t.data_ptr()), B, t.shape[-1], ld
+
+
+def resample(x, out, taps, up, down, *, in0=0, m0=0, track_len=None):
+    """Polyphase sample-rate conversion (vqa_resample, include/vqa.h): x (n_in,) or (B, n_in), fp32 or int16 (read as
+    x * 2^-15), holds samples [in0, in0 + n_in) of tracks of track_len samples (default: in0 + n_in); out (n_out,) or
+    (B, n_out) fp32 receives outputs [m0, m0 + n_out); taps is the contiguous (up, P) fp32 table. x and out may be
+    column slices of wider tensors."""
+    if x.dtype == torch.float32:
+        code = RESAMPLE_F32
+    elif x.dtype == torch.int16:
+        code = RESAMPLE_I16
+    else:
+        raise VQAError(f"resample: x is float32 or int16 (got {x.dtype})")
+    if out.dtype != torch.float32 or taps.dtype != torch.float32:
+        raise VQAError(f"resample: out and taps are float32 (got {out.dtype}, {taps.dtype})")
+    px, B, n_in, ldx = _rows(x, "x")
+    po, Bo, n_out, ldo = _rows(out, "out")
+    if Bo != B:
+        raise VQAError(f"resample: x has {B} rows, out {Bo}")
+    if taps.dim() != 2 or taps.shape[0] != int(up):
+        raise VQAError(f"resample: taps is (up, taps_per_phase) = ({int(up)}, P) (got shape {tuple(taps.shape)})")
+    track_len = int(in0) + n_in if track_len is None else int(track_len)
+    _check(lib().vqa_resample(px, code, ldx, int(in0), n_in, track_len, po, ldo, int(m0), n_out, B, int(up),
+                              int(down), ptr(taps), taps.shape[1], stream()), "vqa_resample")
+
+
+def resample_route(up, down, taps_per_phase):
+    """(table_in_lds, tile_outputs) of a vqa_resample call with these rates and taps: whether the tap table is
+    staged in LDS (else it is read from global memory) and the outputs a workgroup computes. Host-only."""
+    lds, tile = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().vqa_resample_route(int(up), int(down), int(taps_per_phase), ctypes.byref(lds), ctypes.byref(tile)),
+           "vqa_resample_route")
+    return bool(lds.value), tile.value
 
 
 def _int_array(vals):
