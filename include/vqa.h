@@ -470,8 +470,34 @@ int vqa_seqlin_fwd_ln_prepped(const void* x, int64_t ldx, const float* gamma, co
                               const void* wp, const float* bias, const void* residual, int64_t ldr, void* y,
                               int64_t ldy, int nseq, int T, int K, int N, int taps, int dir, int dtype,
                               vqa_stream_t stream);
+/* What a sequence-linear call would run. Host-only: nothing is launched or allocated and no pointer is read
+ * (pointers count for being null or not and for their alignment); the only device query is the CU count, which
+ * sizes the grid (256 is assumed when there is no device). The arguments are those of the three entry points above taken
+ * together: w (raw fp32 weights, vqa_seqlin_fwd) or wp (a prepared image, vqa_seqlin_fwd_prepped; wtrans is then
+ * ignored), and layernorm != 0 for vqa_seqlin_fwd_ln_prepped. Answered by the function the launch itself
+ * follows; returns the VQA_E_* code the call would return before launching anything.
+ *   direct = 1  the persistent kernel: the prepared image of every tap staged once per workgroup in LDS, tiles of
+ *               tile_rows = 16 * waves rows walked with a stride of `workgroups` (a workgroup takes more than one
+ *               tile when tiles > workgroups). Taken for a prepared image with (K, taps) in {(32,1), (128,1),
+ *               (96,3), (128,3)} that fits LDS and, for 1 tap, 16-byte aligned rows of y and of the residual.
+ *   direct = 0  the staged kernel: one tap's weights (raw or prepared) in LDS at a time, one 128-row tile per
+ *               workgroup. A shape whose tiles exceed 160 KiB of LDS is refused with VQA_E_UNSUPPORTED.
+ * out_tiles is the kernel's compile-time count of 16-channel output tiles (2 for N <= 32, else 8); waves is 8 only
+ * for the direct form at N >= 96. */
+typedef struct {
+  int direct, waves, tile_rows, workgroups, tiles, out_tiles;
+  int64_t lds_bytes;
+} vqa_seqlin_route_info;
+int vqa_seqlin_route(const void* x, int64_t ldx, const float* w, const void* wp, const float* bias,
+                     const void* residual, int64_t ldr, void* y, int64_t ldy, int nseq, int T, int K, int N, int taps,
+                     int dir, int wtrans, int accumulate, int dtype, int layernorm, vqa_seqlin_route_info* route);
 /* dW[tap][k][n] = sum_t x[t-(taps-1-tap)][k] dy[t][n], db = sum_t dy[t] (deterministic partials; desc != NULL
- * defers the reduction as for the conv weight gradients). K <= 128, N <= 128, multiples of 16. */
+ * defers the reduction as for the conv weight gradients). K <= 128, N <= 128, multiples of 16.
+ * vqa_seqlin_wgrad_plan (host only; sized by the CU count as above): each sequence is cut into `segs` segments of seg_rows rows (a multiple of the
+ * 64-row chunk), one workgroup and one partial row each; pairs_per_wave is the kernel's compile-time count of
+ * (tap, 16-channel k-tile) pairs per wave, 1, 2 or 6. */
+int vqa_seqlin_wgrad_plan(int nseq, int T, int K, int N, int taps, int dtype, int* seg_rows, int* segs,
+                          int* pairs_per_wave);
 size_t vqa_seqlin_wgrad_workspace(int nseq, int T, int K, int N, int taps);
 int vqa_seqlin_wgrad(const void* x, int64_t ldx, const void* dy, int64_t lddy, float* dw, float* db, int nseq, int T,
                      int K, int N, int taps, int dtype, void* workspace, size_t ws_bytes, vqa_partials_desc* desc,
@@ -525,6 +551,9 @@ int vqa_attn_bwd(const void* q, const void* k, const void* v, const void* o, con
 int vqa_head_wt(const float* w, void* wt, int K, int V, int dtype, vqa_stream_t stream);
 int vqa_head_fwd(const void* x, const void* wt, const float* bias, const int64_t* targets, float* lse, int64_t* amax,
                  float* loss_row, float* correct, int64_t M, int K, int V, int dtype, vqa_stream_t stream);
+/* vqa_head_bwd_plan (host only; sized by the CU count as above): the weight gradient runs `segs` row segments of seg_rows rows (a multiple of
+ * the 64-row chunk) per 64-wide vocabulary tile, one partial row per segment. */
+int vqa_head_bwd_plan(int64_t M, int K, int V, int* segs, int64_t* seg_rows);
 size_t vqa_head_bwd_workspace(int64_t M, int K, int V);
 int vqa_head_bwd(const void* x, const void* wt, const float* bias, const int64_t* targets, const float* lse,
                  float inv_count, void* dx, float* dw, float* db, int64_t M, int K, int V, int dtype, void* workspace,

@@ -6,6 +6,9 @@ logits of FMHABasedAutoregressiveModel, Prior.train_step (two teacher-forcing pa
 the persistent decode kernel (teacher-forced logits and free Gumbel-max sampling vs the reference's full
 recompute sampler), bf16 loss agreement and graph replay.
 Tolerances: fp32 1e-5 (kernels, relative to max |ref|), 2e-4 end to end; bf16 2e-2.
+Every route, tile count and edge of the sequence-linear family, the head and the glue kernels is checked at kernel
+level in tests/test_gpu_seqlin.py, tests/test_gpu_head.py and tests/test_gpu_prior_glue.py (host side:
+tests/test_prior_parity_host.py).
 """
 import math
 import os

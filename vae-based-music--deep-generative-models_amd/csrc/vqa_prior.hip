@@ -1887,50 +1887,83 @@ static size_t wgrad_lds(int K, int N, int taps, int esz) {
   return ((size_t)(64 + taps - 1) * (K + 16 / esz) + (size_t)64 * (N + 16 / esz)) * esz;
 }
 
-template <class T>
-static int launch_seqlin(const SeqLinArgs& a, hipStream_t s) {
+// The (K, taps) pairs seqlin_d_kernel is instantiated for
+#define VQA_SD_SHAPES(X) X(32, 1) X(128, 1) X(96, 3) X(128, 3)
+
+// What a sequence-linear call runs, settled on the host from the arguments alone (vqa_seqlin_route reports it; the
+// launch below follows it): the persistent direct form (a prepared image of every tap in LDS) or the staged form
+// (one tap's weights in LDS at a time, from raw fp32 weights or a prepared image), with its geometry.
+struct SeqlinPlan {
+  int direct, waves, tile_rows, workgroups, tiles, nt;
+  size_t lds;
+};
+
+static int seqlin_plan(const SeqLinArgs& a, int esz, SeqlinPlan& p) {
+  constexpr size_t kLdsMax = 160 * 1024;
   if (a.wp) {
     // wide outputs: 8 waves per workgroup share one staged weight image (one workgroup per CU); narrow ones:
     // 4 waves, two workgroups per CU (measured per shape, tools/seqlin_time.py)
     const bool n2 = a.N <= 32, w8 = a.N >= 96;
     const int waves = w8 ? 8 : 4, max_per_cu = w8 ? 1 : 2;
-    const int KS = a.K + 16 / (int)sizeof(T);
-    const size_t lds = (size_t)a.taps * a.N * KS * sizeof(T) +
+    const int KS = a.K + 16 / esz;
+    const size_t lds = (size_t)a.taps * a.N * KS * esz +
                        (a.taps == 1 ? (size_t)waves * 16 * (a.N + kSdEpad) * sizeof(float) : 0) +
                        (size_t)(2 * a.K + a.N) * sizeof(float);  // LayerNorm slots (used or not) + the bias
-    const void* fn = nullptr;
-#define VQA_SD(KK, TT)                                                                                         \
-    if (a.K == KK && a.taps == TT)                                                                           \
-      fn = n2 ? (const void*)seqlin_d_kernel<T, KK, TT, 2, 4>                                                \
-              : w8 ? (const void*)seqlin_d_kernel<T, KK, TT, 8, 8> : (const void*)seqlin_d_kernel<T, KK, TT, 8, 4>;
-    VQA_SD(32, 1) VQA_SD(128, 1) VQA_SD(96, 3) VQA_SD(128, 3)
+    bool inst = false;
+#define VQA_SD(KK, TT) inst = inst || (a.K == KK && a.taps == TT);
+    VQA_SD_SHAPES(VQA_SD)
 #undef VQA_SD
     // the 1-tap epilogue stores (and reads the residual) in whole 16-byte chunks
-    const int vec = 16 / (int)sizeof(T);
+    const int vec = 16 / esz;
     const bool chunks = a.taps != 1 || (a.ldy % vec == 0 && ((uintptr_t)a.y & 15) == 0 &&
                                         (!a.r || (a.ldr % vec == 0 && ((uintptr_t)a.r & 15) == 0)));
-    if (fn && chunks && lds <= 160 * 1024) {
-      if (int rc = raise_dyn_lds(fn, lds, "prior")) return rc;
-      SeqLinArgs c = a;
-      c.tiles_per_seq = (a.T + 16 * waves - 1) / (16 * waves);
-      int ntiles = a.nseq * c.tiles_per_seq;
-      const int per_cu = std::max(1, std::min<int>(max_per_cu, (int)(160 * 1024 / lds)));
-      const int nwg = std::min(ntiles, cu_count() * per_cu);
-      void* args[] = {&c, &ntiles};
-      (void)hipLaunchKernel(fn, dim3(nwg), dim3(64 * waves), args, lds, s);
-      VQA_LAUNCHED("seqlin_d_kernel");
+    if (inst && chunks && lds <= kLdsMax) {
+      const int tps = (a.T + 16 * waves - 1) / (16 * waves), ntiles = a.nseq * tps;
+      const int per_cu = std::max(1, std::min<int>(max_per_cu, (int)(kLdsMax / lds)));
+      p = SeqlinPlan{1, waves, 16 * waves, std::min(ntiles, cu_count() * per_cu), ntiles, n2 ? 2 : 8, lds};
       return VQA_OK;
     }
-    // weights too large for one LDS image: stage per tap from the prepared image
+    // weights too large for one LDS image (or no direct instantiation, or unaligned 1-tap rows): stage per tap
+    // from the prepared image
   }
   VQA_REQUIRE(!a.lng, VQA_E_UNSUPPORTED, "seqlin_fwd_ln_prepped: K=%d N=%d taps=%d has no fused form", a.K, a.N,
               a.taps);
-  const void* fn = a.N <= 32 ? (const void*)seqlin_kernel<T, 2> : (const void*)seqlin_kernel<T, 8>;
-  const size_t lds = seqlin_lds(a.K, a.N, a.taps, sizeof(T));
-  if (int rc = raise_dyn_lds(fn, lds, "prior")) return rc;
+  const size_t lds = seqlin_lds(a.K, a.N, a.taps, esz);
+  VQA_REQUIRE(lds <= kLdsMax, VQA_E_UNSUPPORTED,
+              "seqlin_fwd: K=%d N=%d taps=%d needs %zu bytes of LDS for its tiles (limit %zu)", a.K, a.N, a.taps, lds,
+              kLdsMax);
+  const int ntiles = a.nseq * ((a.T + kSlRows - 1) / kSlRows);
+  p = SeqlinPlan{0, 4, kSlRows, ntiles, ntiles, a.N <= 32 ? 2 : 8, lds};
+  return VQA_OK;
+}
+
+template <class T>
+static int launch_seqlin(const SeqLinArgs& a, hipStream_t s) {
+  SeqlinPlan p;
+  if (int rc = seqlin_plan(a, (int)sizeof(T), p)) return rc;
   SeqLinArgs c = a;
+  if (p.direct) {
+    const void* fn = nullptr;
+#define VQA_SD(KK, TT)                                                                                         \
+    if (a.K == KK && a.taps == TT)                                                                           \
+      fn = p.nt == 2 ? (const void*)seqlin_d_kernel<T, KK, TT, 2, 4>                                         \
+                     : p.waves == 8 ? (const void*)seqlin_d_kernel<T, KK, TT, 8, 8>                          \
+                                    : (const void*)seqlin_d_kernel<T, KK, TT, 8, 4>;
+    VQA_SD_SHAPES(VQA_SD)
+#undef VQA_SD
+    VQA_REQUIRE(fn, VQA_E_UNSUPPORTED, "seqlin_fwd: no direct kernel for K=%d taps=%d", a.K, a.taps);
+    if (int rc = raise_dyn_lds(fn, p.lds, "prior")) return rc;
+    c.tiles_per_seq = (a.T + p.tile_rows - 1) / p.tile_rows;
+    int ntiles = p.tiles;
+    void* args[] = {&c, &ntiles};
+    (void)hipLaunchKernel(fn, dim3(p.workgroups), dim3(64 * p.waves), args, p.lds, s);
+    VQA_LAUNCHED("seqlin_d_kernel");
+    return VQA_OK;
+  }
+  const void* fn = p.nt == 2 ? (const void*)seqlin_kernel<T, 2> : (const void*)seqlin_kernel<T, 8>;
+  if (int rc = raise_dyn_lds(fn, p.lds, "prior")) return rc;
   void* args[] = {&c};
-  (void)hipLaunchKernel(fn, dim3(a.nseq * a.tiles_per_seq), dim3(256), args, lds, s);
+  (void)hipLaunchKernel(fn, dim3(p.workgroups), dim3(256), args, p.lds, s);
   VQA_LAUNCHED("seqlin_kernel");
   return VQA_OK;
 }
@@ -1973,9 +2006,10 @@ extern "C" int vqa_seqlin_prep(const vqa_seqlin_prep_desc* descs, int count, int
   return VQA_OK;
 }
 
-static int seqlin_launch(const void* x, int64_t ldx, const float* w, const void* wp, const float* bias,
-                         const void* residual, int64_t ldr, void* y, int64_t ldy, int nseq, int T, int K, int N,
-                         int taps, int dir, int wtrans, int accumulate, int dtype, hipStream_t s) {
+// argument checks of every sequence-linear entry point (host only) -> the kernels' argument block
+static int seqlin_args(const void* x, int64_t ldx, const float* w, const void* wp, const float* bias,
+                       const void* residual, int64_t ldr, void* y, int64_t ldy, int nseq, int T, int K, int N,
+                       int taps, int dir, int wtrans, int accumulate, int dtype, SeqLinArgs& a) {
   VQA_ARG(x && (w || wp) && y && nseq > 0 && T > 0 && (taps == 1 || taps == 3) && (dir == -1 || dir == 1),
           "seqlin_fwd: bad arguments");
   VQA_ARG(pr_dt(dtype), "seqlin_fwd: unknown dtype %d", dtype);
@@ -1985,9 +2019,56 @@ static int seqlin_launch(const void* x, int64_t ldx, const float* w, const void*
   VQA_ARG(ldx % vec == 0 && ldy % 4 == 0 && (!residual || ldr % 4 == 0) && ldx >= K && ldy >= N,
           "seqlin_fwd: strides must keep 16-byte rows");
   VQA_ARG(((uintptr_t)(w ? (const void*)w : wp) & 15) == 0, "seqlin_fwd: weights must be 16-byte aligned");
-  SeqLinArgs a{x, w, wp, bias, residual, y, ldx, ldr, ldy, nseq, T, K, N, taps, dir, wtrans, accumulate,
-               (T + kSlRows - 1) / kSlRows};
+  a = SeqLinArgs{x, w, wp, bias, residual, y, ldx, ldr, ldy, nseq, T, K, N, taps, dir, wtrans, accumulate,
+                 (T + kSlRows - 1) / kSlRows};
+  return VQA_OK;
+}
+
+static int seqlin_ln_args(const void* x, int64_t ldx, const float* gamma, const float* beta, float eps, const void* wp,
+                          const float* bias, const void* residual, int64_t ldr, void* y, int64_t ldy, int nseq, int T,
+                          int K, int N, int taps, int dir, int dtype, SeqLinArgs& a) {
+  VQA_ARG(x && wp && y && gamma && beta && nseq > 0 && T > 0 && (taps == 1 || taps == 3) && (dir == -1 || dir == 1),
+          "seqlin_fwd_ln_prepped: bad arguments");
+  VQA_REQUIRE(dtype == VQA_BF16 && K == 128 && N > 0 && N <= 128 && N % 16 == 0, VQA_E_UNSUPPORTED,
+              "seqlin_fwd_ln_prepped: dtype %d K=%d N=%d unsupported (bf16, K = 128)", dtype, K, N);
+  VQA_ARG(ldx % 8 == 0 && ldx >= K && ldy >= N && ldy % 4 == 0 && (!residual || ldr % 4 == 0),
+          "seqlin_fwd_ln_prepped: strides must keep 16-byte rows");
+  VQA_ARG(((uintptr_t)wp & 15) == 0, "seqlin_fwd_ln_prepped: weights must be 16-byte aligned");
+  a = SeqLinArgs{x, nullptr, wp, bias, residual, y, ldx, ldr, ldy, nseq, T, K, N, taps, dir, 0, 0,
+                 (T + kSlRows - 1) / kSlRows, gamma, beta, eps};
+  return VQA_OK;
+}
+
+static int seqlin_launch(const void* x, int64_t ldx, const float* w, const void* wp, const float* bias,
+                         const void* residual, int64_t ldr, void* y, int64_t ldy, int nseq, int T, int K, int N,
+                         int taps, int dir, int wtrans, int accumulate, int dtype, hipStream_t s) {
+  SeqLinArgs a;
+  if (int rc = seqlin_args(x, ldx, w, wp, bias, residual, ldr, y, ldy, nseq, T, K, N, taps, dir, wtrans, accumulate,
+                           dtype, a))
+    return rc;
   return dtype == VQA_BF16 ? launch_seqlin<bf16>(a, s) : launch_seqlin<float>(a, s);
+}
+
+extern "C" int vqa_seqlin_route(const void* x, int64_t ldx, const float* w, const void* wp, const float* bias,
+                                const void* residual, int64_t ldr, void* y, int64_t ldy, int nseq, int T, int K, int N,
+                                int taps, int dir, int wtrans, int accumulate, int dtype, int layernorm,
+                                vqa_seqlin_route_info* route) {
+  VQA_ARG(route, "seqlin_route: null route");
+  SeqLinArgs a;
+  if (layernorm) {
+    // the fused form's LayerNorm parameters are only tested for presence: stand-ins that are never read
+    static const float one = 1.f;
+    if (int rc = seqlin_ln_args(x, ldx, &one, &one, 0.f, wp, bias, residual, ldr, y, ldy, nseq, T, K, N, taps, dir,
+                                dtype, a))
+      return rc;
+  } else if (int rc = seqlin_args(x, ldx, w, wp, bias, residual, ldr, y, ldy, nseq, T, K, N, taps, dir, wtrans,
+                                  accumulate, dtype, a)) {
+    return rc;
+  }
+  SeqlinPlan p;
+  if (int rc = seqlin_plan(a, dtype == VQA_BF16 ? 2 : 4, p)) return rc;
+  *route = vqa_seqlin_route_info{p.direct, p.waves, p.tile_rows, p.workgroups, p.tiles, p.nt, (int64_t)p.lds};
+  return VQA_OK;
 }
 
 extern "C" int vqa_seqlin_fwd(const void* x, int64_t ldx, const float* w, const float* bias, const void* residual,
@@ -2010,15 +2091,10 @@ extern "C" int vqa_seqlin_fwd_ln_prepped(const void* x, int64_t ldx, const float
                                          float eps, const void* wp, const float* bias, const void* residual,
                                          int64_t ldr, void* y, int64_t ldy, int nseq, int T, int K, int N, int taps,
                                          int dir, int dtype, vqa_stream_t stream) {
-  VQA_ARG(x && wp && y && gamma && beta && nseq > 0 && T > 0 && (taps == 1 || taps == 3) && (dir == -1 || dir == 1),
-          "seqlin_fwd_ln_prepped: bad arguments");
-  VQA_REQUIRE(dtype == VQA_BF16 && K == 128 && N > 0 && N <= 128 && N % 16 == 0, VQA_E_UNSUPPORTED,
-              "seqlin_fwd_ln_prepped: dtype %d K=%d N=%d unsupported (bf16, K = 128)", dtype, K, N);
-  VQA_ARG(ldx % 8 == 0 && ldx >= K && ldy >= N && ldy % 4 == 0 && (!residual || ldr % 4 == 0),
-          "seqlin_fwd_ln_prepped: strides must keep 16-byte rows");
-  VQA_ARG(((uintptr_t)wp & 15) == 0, "seqlin_fwd_ln_prepped: weights must be 16-byte aligned");
-  SeqLinArgs a{x, nullptr, wp, bias, residual, y, ldx, ldr, ldy, nseq, T, K, N, taps, dir, 0, 0,
-               (T + kSlRows - 1) / kSlRows, gamma, beta, eps};
+  SeqLinArgs a;
+  if (int rc = seqlin_ln_args(x, ldx, gamma, beta, eps, wp, bias, residual, ldr, y, ldy, nseq, T, K, N, taps, dir,
+                              dtype, a))
+    return rc;
   return launch_seqlin<bf16>(a, (hipStream_t)stream);
 }
 
@@ -2029,21 +2105,40 @@ extern "C" size_t vqa_seqlin_wgrad_workspace(int nseq, int T, int K, int N, int 
   return (size_t)nseq * segs * ((size_t)taps * K * N + N) * sizeof(float);
 }
 
+// shape checks and launch geometry of vqa_seqlin_wgrad (host only; vqa_seqlin_wgrad_plan reports them)
+static int wgrad_route(int nseq, int T, int K, int N, int taps, int dtype, int& seg_rows, int& segs, int& ppw) {
+  VQA_ARG(nseq > 0 && T > 0 && (taps == 1 || taps == 3), "seqlin_wgrad: bad arguments");
+  VQA_ARG(pr_dt(dtype), "seqlin_wgrad: unknown dtype %d", dtype);
+  VQA_REQUIRE(K > 0 && K % 16 == 0 && K <= 128 && N > 0 && N % 16 == 0 && N <= 128 && (taps * K / 16 + 3) / 4 <= 6,
+              VQA_E_UNSUPPORTED, "seqlin_wgrad: K=%d N=%d taps=%d unsupported", K, N, taps);
+  wgrad_plan(nseq, T, seg_rows, segs);
+  const int need = (taps * K / 16 + 3) / 4;  // (tap, k-tile) pairs of the busiest wave
+  ppw = need <= 1 ? 1 : need <= 2 ? 2 : 6;   // the instantiations of seqlin_wgrad_kernel
+  return VQA_OK;
+}
+
+extern "C" int vqa_seqlin_wgrad_plan(int nseq, int T, int K, int N, int taps, int dtype, int* seg_rows, int* segs,
+                                     int* pairs_per_wave) {
+  VQA_ARG(seg_rows && segs && pairs_per_wave, "seqlin_wgrad_plan: null seg_rows, segs or pairs_per_wave");
+  int sr, sg, ppw;
+  if (int rc = wgrad_route(nseq, T, K, N, taps, dtype, sr, sg, ppw)) return rc;
+  *seg_rows = sr;
+  *segs = sg;
+  *pairs_per_wave = ppw;
+  return VQA_OK;
+}
+
 extern "C" int vqa_seqlin_wgrad(const void* x, int64_t ldx, const void* dy, int64_t lddy, float* dw, float* db,
                                 int nseq, int T, int K, int N, int taps, int dtype, void* workspace, size_t ws_bytes,
                                 vqa_partials_desc* desc, vqa_stream_t stream) {
-  VQA_ARG(x && dy && dw && nseq > 0 && T > 0 && (taps == 1 || taps == 3), "seqlin_wgrad: bad arguments");
-  VQA_ARG(pr_dt(dtype), "seqlin_wgrad: unknown dtype %d", dtype);
+  VQA_ARG(x && dy && dw, "seqlin_wgrad: bad arguments");
+  int seg_rows, segs, ppw;
+  if (int rc = wgrad_route(nseq, T, K, N, taps, dtype, seg_rows, segs, ppw)) return rc;
   const int esz = dtype == VQA_BF16 ? 2 : 4, vec = 16 / esz;
-  VQA_REQUIRE(K % 16 == 0 && K <= 128 && N % 16 == 0 && N <= 128 && (taps * K / 16 + 3) / 4 <= 6, VQA_E_UNSUPPORTED,
-              "seqlin_wgrad: K=%d N=%d taps=%d unsupported", K, N, taps);
   VQA_ARG(ldx % vec == 0 && lddy % vec == 0, "seqlin_wgrad: strides must keep 16-byte rows");
   const size_t need = vqa_seqlin_wgrad_workspace(nseq, T, K, N, taps);
   VQA_ARG(workspace && ws_bytes >= need, "seqlin_wgrad: workspace %zu < %zu", ws_bytes, need);
-  int seg_rows, segs;
-  wgrad_plan(nseq, T, seg_rows, segs);
   SeqWgArgs a{x, dy, (float*)workspace, ldx, lddy, nseq, T, K, N, taps, seg_rows, segs};
-  const int ppw = (taps * K / 16 + 3) / 4;
   const void* fn = dtype == VQA_BF16 ? wgrad_fn<bf16>(ppw, N) : wgrad_fn<float>(ppw, N);
   const size_t lds = wgrad_lds(K, N, taps, esz);
   if (int rc = raise_dyn_lds(fn, lds, "prior")) return rc;
@@ -2238,6 +2333,24 @@ static int head_segs(int64_t M, int V) {
   return (int)std::min<long long>(want, (M + 63) / 64);
 }
 
+// row segments of head_bwd_dw_kernel: nseg segments of seg_rows rows (a multiple of its 64-row chunk)
+static void head_plan(int64_t M, int V, int& nseg, long long& seg_rows) {
+  const int segs = head_segs(M, V);
+  seg_rows = ((M + segs - 1) / segs + 63) / 64 * 64;
+  nseg = (int)((M + seg_rows - 1) / seg_rows);
+}
+
+extern "C" int vqa_head_bwd_plan(int64_t M, int K, int V, int* segs, int64_t* seg_rows) {
+  VQA_ARG(segs && seg_rows, "head_bwd_plan: null segs or seg_rows");
+  VQA_ARG(M > 0 && K == HK && V > 0, "head_bwd_plan: bad arguments");
+  int nseg;
+  long long sr;
+  head_plan(M, V, nseg, sr);
+  *segs = nseg;
+  *seg_rows = sr;
+  return VQA_OK;
+}
+
 extern "C" size_t vqa_head_bwd_workspace(int64_t M, int K, int V) {
   if (M < 1 || K < 1 || V < 1) return 0;
   return (size_t)head_segs(M, V) * ((size_t)K * V + V) * sizeof(float);
@@ -2250,8 +2363,10 @@ extern "C" int vqa_head_bwd(const void* x, const void* wt, const float* bias, co
           "head_bwd: bad arguments");
   const size_t need = vqa_head_bwd_workspace(M, K, V);
   VQA_ARG(workspace && ws_bytes >= need, "head_bwd: workspace %zu < %zu", ws_bytes, need);
-  const int segs = head_segs(M, V), nvt = (V + 63) / 64;
-  const long long seg_rows = ((M + segs - 1) / segs + 63) / 64 * 64;
+  const int nvt = (V + 63) / 64;
+  int nseg;
+  long long seg_rows;
+  head_plan(M, V, nseg, seg_rows);
   HeadArgs a{x, wt, bias, targets, (float*)lse, nullptr, nullptr, nullptr, dx, (float*)workspace, (long long)M, V,
              (int)seg_rows, inv_count};
   const int esz = dtype == VQA_BF16 ? 2 : 4, S = HK + 16 / esz;
@@ -2259,7 +2374,6 @@ extern "C" int vqa_head_bwd(const void* x, const void* wt, const float* bias, co
   int rc = dtype == VQA_BF16 ? launch_head<bf16>(1, a, (unsigned)((M + 127) / 128), (size_t)(128 + 64) * S * esz, s)
                              : launch_head<float>(1, a, (unsigned)((M + 127) / 128), (size_t)(128 + 64) * S * esz, s);
   if (rc) return rc;
-  const int nseg = (int)((M + seg_rows - 1) / seg_rows);
   rc = dtype == VQA_BF16 ? launch_head<bf16>(2, a, (unsigned)(nseg * nvt), (size_t)128 * S * esz, s)
                          : launch_head<float>(2, a, (unsigned)(nseg * nvt), (size_t)128 * S * esz, s);
   if (rc) return rc;

@@ -40,6 +40,7 @@ EXPORTED = [
     "vqa_embedding_fwd", "vqa_embedding_bwd", "vqa_embedding_bwd_workspace", "vqa_layernorm_fwd",
     "vqa_layernorm_bwd", "vqa_layernorm_bwd_workspace",
     "vqa_seqlin_fwd", "vqa_seqlin_prep", "vqa_seqlin_fwd_prepped", "vqa_seqlin_fwd_ln_prepped", "vqa_seqlin_wgrad_workspace", "vqa_seqlin_wgrad", "vqa_prior_embed_fwd", "vqa_colsum",
+    "vqa_seqlin_route", "vqa_seqlin_wgrad_plan", "vqa_head_bwd_plan",
     "vqa_axpy", "vqa_dropout", "vqa_scale_f32", "vqa_tf_mix", "vqa_attn_fwd", "vqa_attn_bwd", "vqa_head_wt",
     "vqa_head_fwd", "vqa_head_bwd_workspace", "vqa_head_bwd", "vqa_rowsum_workspace", "vqa_rowsum", "vqa_prior_decode_cache_bytes",
     "vqa_prior_decode", "vqa_prior_decode_primed",
@@ -127,6 +128,9 @@ _SIGS = {
     "vqa_seqlin_prep": (_I, [_P, _I, _I, _P]),
     "vqa_seqlin_fwd_prepped": (_I, [_P, _L, _P, _P, _P, _L, _P, _L] + [_I] * 8 + [_P]),
     "vqa_seqlin_fwd_ln_prepped": (_I, [_P, _L, _P, _P, ctypes.c_float, _P, _P, _P, _L, _P, _L] + [_I] * 7 + [_P]),
+    "vqa_seqlin_route": (_I, [_P, _L, _P, _P, _P, _P, _L, _P, _L] + [_I] * 10 + [_P]),
+    "vqa_seqlin_wgrad_plan": (_I, [_I] * 6 + [_P, _P, _P]),
+    "vqa_head_bwd_plan": (_I, [_L, _I, _I, _P, _P]),
     "vqa_seqlin_wgrad_workspace": (_S, [_I] * 5),
     "vqa_seqlin_wgrad": (_I, [_P, _L, _P, _L, _P, _P] + [_I] * 6 + [_P, _S, _P, _P]),
     "vqa_prior_embed_fwd": (_I, [_P] * 6 + [_I] * 4 + [_F, _F, _U, _L, _P, _I, _P]),
@@ -817,6 +821,47 @@ def seqlin_fwd_ln_prepped(x, gamma, beta, eps, wp, b, y, T, taps=1, dir=-1, resi
     _check(lib().vqa_seqlin_fwd_ln_prepped(px, ldx, ptr(gamma), ptr(beta), float(eps), ptr(wp), ptr(b), pr, ldr, py,
                                            ldy, rows // T, T, K, N, taps, dir, dtype_code(x.dtype), stream()),
            "vqa_seqlin_fwd_ln_prepped")
+
+
+class SeqlinRouteInfo(ctypes.Structure):
+    """vqa_seqlin_route_info (include/vqa.h)."""
+    _fields_ = [("direct", ctypes.c_int), ("waves", ctypes.c_int), ("tile_rows", ctypes.c_int),
+                ("workgroups", ctypes.c_int), ("tiles", ctypes.c_int), ("out_tiles", ctypes.c_int),
+                ("lds_bytes", ctypes.c_int64)]
+
+    def __repr__(self):
+        return "SeqlinRoute(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
+def seqlin_route(x, y, T, w=None, wp=None, b=None, taps=1, dir=-1, wtrans=False, residual=None, accumulate=False,
+                 layernorm=False):
+    """vqa_seqlin_route for the seqlin_fwd (w) / seqlin_fwd_prepped (wp) / seqlin_fwd_ln_prepped (wp, layernorm)
+    call with these tensors: the SeqlinRouteInfo the launch would follow. Host-only, nothing is launched."""
+    px, ldx = rptr(x)
+    py, ldy = rptr(y)
+    pr, ldr = rptr(residual) if residual is not None else (None, 0)
+    K, N = x.shape[-1], y.shape[-1]
+    rows = x.numel() // K
+    r = SeqlinRouteInfo()
+    _check(lib().vqa_seqlin_route(px, ldx, ptr(w), ptr(wp), ptr(b), pr, ldr, py, ldy, rows // T, T, K, N, taps, dir,
+                                  int(bool(wtrans)), int(bool(accumulate)), dtype_code(x.dtype),
+                                  int(bool(layernorm)), ctypes.byref(r)), "vqa_seqlin_route")
+    return r
+
+
+def seqlin_wgrad_plan(nseq, T, K, N, taps, dtype):
+    """(seg_rows, segs, pairs_per_wave) of a vqa_seqlin_wgrad call. Host-only."""
+    a, b, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().vqa_seqlin_wgrad_plan(nseq, T, K, N, taps, dtype_code(dtype), ctypes.byref(a), ctypes.byref(b),
+                                       ctypes.byref(c)), "vqa_seqlin_wgrad_plan")
+    return a.value, b.value, c.value
+
+
+def head_bwd_plan(M, K, V):
+    """(segs, seg_rows) of vqa_head_bwd's weight-gradient kernel. Host-only."""
+    a, b = ctypes.c_int(0), ctypes.c_int64(0)
+    _check(lib().vqa_head_bwd_plan(int(M), int(K), int(V), ctypes.byref(a), ctypes.byref(b)), "vqa_head_bwd_plan")
+    return a.value, b.value
 
 
 def seqlin_wgrad(x, dy, dw, db, T, taps=1, deferred=None):
