@@ -174,6 +174,26 @@ int vqa_resblock_bwd(const void* dy, const void* x, const float* wa, const float
                      void* dx, float* dwa, float* dba, float* dwb, float* dbb, int B, int T, int C, int dilation,
                      int dtype, void* workspace, size_t ws_bytes, vqa_partials_desc* desc, vqa_stream_t stream);
 size_t vqa_resblock_bwd_workspace(int B, int T, int C, int dilation, int dtype);
+/* What vqa_resblock_fwd (backward = 0) or vqa_resblock_bwd (backward != 0) would launch. Host-only: nothing is
+ * launched or allocated; the only device query is the CU count, which sizes the grid (256 is assumed when there is no
+ * device). Answered by the function both launches take their plan from; returns the VQA_E_* code the call would
+ * return for these sizes before launching anything.
+ *   tile_rows            output rows per tile. Forward: 176 for the compiled dilations 1, 3, 9, 27, else 128.
+ *                        Backward: 160 for d in {1, 3, 9} with T >= 8192, else 128.
+ *   compiled_dilation    the dilation the kernel instance is compiled for; 0: the runtime-dilation instance
+ *   tiles_per_item       ceil(T / tile_rows); tiles = B * tiles_per_item, numbered item-major
+ *   workgroups           persistent workgroups: min(3 CUs, tiles) forward, min(2 CUs, max(1, tiles / 2)) backward
+ *   tiles_per_workgroup, extra_tile_workgroups
+ *                        workgroup w owns tiles_per_workgroup (+ 1 when w < extra_tile_workgroups) consecutive
+ *                        tiles, starting at w * tiles_per_workgroup + min(w, extra_tile_workgroups)
+ *   partial_rows         backward: weight-gradient partial rows per conv, one per workgroup; forward: 0
+ *   lds_bytes            the launch's dynamic LDS */
+typedef struct {
+  int tile_rows, compiled_dilation, tiles_per_item, tiles, workgroups, tiles_per_workgroup, extra_tile_workgroups,
+      partial_rows;
+  int64_t lds_bytes;
+} vqa_resblock_plan_info;
+int vqa_resblock_plan(int B, int T, int C, int dilation, int dtype, int backward, vqa_resblock_plan_info* plan);
 
 /* ---- decoder tail: the last Conv1DTranspose (K=4, stride 2, C -> Cu) of the last decoder block followed by
  *      the decoder's output Conv1D (K=3, Cu -> 1), encdec.py:67-68 then :148, with nothing in between, run as

@@ -5,11 +5,19 @@ Forward: y (and relu(h)) bit-identical to the two-call unfused path (same MFMA o
 h). Backward (h recomputed from x): dx and the four weight gradients against fp64 autograd with the ReLU
 masks of the GPU's own h — relative L2 1e-5 in fp32; in bf16 against the unfused backward within 2e-2.
 Ragged lengths, T shorter than a tile, every dilation of the model (1, 3, 9, 27) and the largest supported.
+
+Per-element parity (tests/resblock_parity_ref.py): the backward, fp32 and bf16, at the smallest shape of every tile
+plan (asserted through vqa_resblock_plan), against the fp64 reference with its own ReLU masks, dx element by element
+and the weight gradients to the fp32 bound; a workgroup's run crossing from one item's ragged last tile into the next
+item; the persistent loops' steady state (>= 4 tiles per workgroup with extras, one checked item replicated, so no
+large reference); the forward looping above 3 workgroups per CU; ba = NULL; exact zeros in x. Inputs and dx sit
+between NaN guard bands and the gradient buffers start as NaN.
 """
 import numpy as np
 import pytest
 import torch
 
+import resblock_parity_ref as R
 import vqa_lib as V
 from oracle.vqvae_ref import conv1d as ref_conv
 
@@ -180,3 +188,187 @@ def test_unsupported(cuda):
     assert not V.resblock_supported(64, 1, V.BF16)
     assert not V.resblock_supported(32, 33, V.BF16)
     assert V.resblock_supported(32, 27, V.BF16) and V.resblock_supported(32, 27, V.F32)
+
+
+# ------------------------------------------------------------------ per-element parity on every tile plan
+GUARD = 4096   # NaN elements on either side of x, dy and dx
+DTS = [torch.float32, torch.bfloat16]
+DT_IDS = ["fp32", "bf16"]
+
+
+def _guarded(t, cuda):
+    """a device copy of t between two NaN bands -> (the copy, the whole buffer)"""
+    buf = torch.full((t.numel() + 2 * GUARD,), float("nan"), dtype=t.dtype, device=cuda)
+    view = buf[GUARD:GUARD + t.numel()].view(t.shape)
+    view.copy_(t)
+    return view, buf
+
+
+def _bands_intact(buf):
+    return bool(torch.isnan(buf[:GUARD]).all()) and bool(torch.isnan(buf[-GUARD:]).all())
+
+
+def _dev(p, cuda):
+    q = {k: (None if v is None else v.to(cuda).contiguous()) for k, v in p.items()}
+    q["x"], q["x_buf"] = _guarded(p["x"], cuda)
+    q["dy"], q["dy_buf"] = _guarded(p["dy"], cuda)
+    return q
+
+
+def _bwd_guarded(q, d, deferred=False):
+    """the fused backward with dx between NaN bands and NaN-filled gradient buffers -> (dx, grads)"""
+    x = q["x"]
+    dx, dx_buf = _guarded(torch.zeros(x.shape, dtype=x.dtype), x.device)
+    dx.fill_(float("nan"))
+    g = {k: torch.full(s, float("nan"), device=x.device) for k, s in
+         (("wa", (3, C, C)), ("ba", (C,)), ("wb", (3, C, C)), ("bb", (C,)))}
+    dfr = V.Deferred() if deferred else None
+    V.resblock_bwd(q["dy"], x, q["wa"], q["ba"], q["wb"], q["bb"], dx, g["wa"], g["ba"], g["wb"], g["bb"], d, dfr)
+    if dfr is not None:
+        dfr.flush()
+    torch.cuda.synchronize()
+    assert _bands_intact(dx_buf) and not bool(torch.isnan(dx).any())
+    assert _bands_intact(q["x_buf"]) and _bands_intact(q["dy_buf"])
+    return dx, g
+
+
+def _assert_parity(name, ref, dx, g):
+    """every output against the reference's per-element tolerance; the figures go to the table first"""
+    ratios = {}
+    for k, got in [("dx", dx)] + [(k, g[k]) for k in R.GRADS]:
+        ratios[k] = ref.ratio(k, got)
+        R.record(k, name, ref.e32[k], ref.c[k], ref.err(k, got), ratios[k])
+    assert ref.s_share <= R.S_MAX
+    for k, r in ratios.items():
+        assert r <= 1.0, f"{name} {k}: err / tolerance = {r:.3f}"
+
+
+def _name(B, T, d, dt, tag=""):
+    return f"B={B} T={T} d={d} {R.dt_name(dt)}{tag}"
+
+
+# (tile rows, compiled dilation) of every backward plan case
+WANT_PLAN = {(1, 8269, 1): (160, 1), (1, 8269, 3): (160, 3), (1, 8269, 9): (160, 9), (1, 8191, 9): (128, 9),
+             (1, 8192, 9): (160, 9), (2, 2049, 27): (128, 27), (3, 129, 32): (128, 0), (1, 300, 2): (128, 0),
+             (1, 1, 27): (128, 27), (1, 5, 27): (128, 27), (1, 27, 27): (128, 27), (1, 1, 1): (128, 1)}
+
+
+@pytest.mark.parametrize("dt", DTS, ids=DT_IDS)
+@pytest.mark.parametrize("B,T,d", R.PLAN_CASES)
+def test_backward_per_element_on_every_plan(cuda, B, T, d, dt):
+    pl = V.resblock_plan(B, T, C, d, dt, True)
+    assert (pl.tile_rows, pl.compiled_dilation) == WANT_PLAN[(B, T, d)], pl
+    assert pl.tiles_per_item == -(-T // pl.tile_rows) and pl.tiles == B * pl.tiles_per_item
+    assert pl.partial_rows == pl.workgroups
+    if (B, T, d) == (2, 2049, 27):
+        assert T - (pl.tiles_per_item - 1) * pl.tile_rows == 1      # a last tile of one row
+    p, ref = R.case(B, T, d, dt, pl.tile_rows)
+    dx, g = _bwd_guarded(_dev(p, cuda), d)
+    _assert_parity(_name(B, T, d, dt), ref, dx, g)
+
+
+@pytest.mark.parametrize("dt", DTS, ids=DT_IDS)
+@pytest.mark.parametrize("B,T,d", R.CROSS_CASES)
+def test_backward_run_crosses_into_the_next_item(cuda, B, T, d, dt):
+    """9 tiles on 4 workgroups, one of them with an extra tile: a run goes from item 1's ragged last tile (44 rows)
+    into item 2's first, prefetching across the boundary."""
+    pl = V.resblock_plan(B, T, C, d, dt, True)
+    assert (pl.tile_rows, pl.tiles_per_item, pl.tiles) == (128, 3, 9), pl
+    assert (pl.workgroups, pl.tiles_per_workgroup, pl.extra_tile_workgroups) == (4, 2, 1), pl
+    runs = [pl.run(w) for w in range(pl.workgroups)]
+    assert runs[-1][1] == pl.tiles
+    assert any(a // pl.tiles_per_item != (b - 1) // pl.tiles_per_item for a, b in runs)
+    p, ref = R.case(B, T, d, dt, pl.tile_rows)
+    dx, g = _bwd_guarded(_dev(p, cuda), d)
+    _assert_parity(_name(B, T, d, dt, " cross"), ref, dx, g)
+
+
+@pytest.mark.parametrize("dt", DTS, ids=DT_IDS)
+@pytest.mark.parametrize("T,d", R.STEADY_CASES)
+def test_backward_steady_state_replicated_item(cuda, T, d, dt):
+    """One checked item replicated B times, B the smallest for which the plan gives every workgroup at least 4
+    tiles and some of them one more: every item's dx is bitwise the single-item launch's (a tile's arithmetic does
+    not depend on its slot), the weight gradients are B times the single item's fp64 reference within the bound (its
+    e32 taken over the fp32 running sum of B copies), and the deferred reduction gives the same bits."""
+    one = V.resblock_plan(1, T, C, d, dt, True)
+    assert one.tile_rows == (160 if d == 9 else 128)
+    B = next(b for b in range(2, 4096) if (lambda q: q.tiles_per_workgroup >= 4 and q.extra_tile_workgroups >= 1)(
+        V.resblock_plan(b, T, C, d, dt, True)))
+    pl = V.resblock_plan(B, T, C, d, dt, True)
+    assert pl.tile_rows == one.tile_rows and pl.tiles_per_workgroup >= 4 and pl.extra_tile_workgroups >= 1, pl
+    p, ref = R.case(1, T, d, dt, one.tile_rows)
+    dx1, g1 = _bwd_guarded(_dev(p, cuda), d)
+    _assert_parity(_name(1, T, d, dt, " single"), ref, dx1, g1)
+    rep = dict(p, x=p["x"].expand(B, T, C).contiguous(), dy=p["dy"].expand(B, T, C).contiguous())
+    q = _dev(rep, cuda)
+    dxB, gB = _bwd_guarded(q, d)
+    assert torch.equal(dxB, dx1.expand(B, T, C))
+    dxD, gD = _bwd_guarded(q, d, deferred=True)
+    assert torch.equal(dxD, dxB)
+    for k in R.GRADS:
+        assert torch.equal(gD[k], gB[k]), k
+        want, allow = B * ref.r[k], B * ref.allow[k]
+        run = torch.zeros_like(ref.lo[k])
+        for _ in range(B):
+            run = run + ref.lo[k]                      # the fp32 running sum of B item sums
+        scale = float(want.abs().max())
+        e32 = float(((run.double() - want).abs() - allow).clamp_min(0).max()) / scale
+        c = max(R.WGRAD_TOL, 8.0 * e32)
+        ratio = ref.ratio(k, gB[k], want, c * scale + allow)
+        R.record(k, _name(B, T, d, dt, " steady"), e32, c, ref.err(k, gB[k], want), ratio)
+        assert ratio <= 1.0, f"{k}: err / tolerance = {ratio:.3f}"
+
+
+@pytest.mark.parametrize("dt", DTS, ids=DT_IDS)
+@pytest.mark.parametrize("T,d", [(2 * 176 + 5, 3), (300, 2)])
+def test_forward_loops_above_three_workgroups_per_cu(cuda, T, d, dt):
+    """B sized from the plan so that every forward workgroup loops over 2 tiles and some over 3 (the prefetch two
+    ahead), runs crossing items: bit-identical to the unfused path."""
+    B = next(b for b in range(1, 1 << 16) if (lambda q: q.tiles_per_workgroup >= 2 and q.extra_tile_workgroups >= 1)(
+        V.resblock_plan(b, T, C, d, dt, False)))
+    pl = V.resblock_plan(B, T, C, d, dt, False)
+    assert (pl.tile_rows, pl.compiled_dilation, pl.tiles_per_item) == ((176, 3, 3) if d == 3 else (128, 0, 3)), pl
+    assert pl.tiles_per_workgroup >= 2 and pl.extra_tile_workgroups >= 1 and pl.partial_rows == 0
+    p = _block(B, T, d, seed=T + d, dt=dt, cuda=cuda)
+    h0, y0 = _unfused_fwd(p, d)
+    h1, y1 = _fused_fwd(p, d)
+    assert torch.equal(y1, y0)
+    assert torch.equal(h1, torch.relu(h0))
+
+
+@pytest.mark.parametrize("dt", DTS, ids=DT_IDS)
+def test_no_bias_a(cuda, dt):
+    """ba = NULL on both entry points: the bits of a zero bias, and the backward within the per-element bound of the
+    reference without b_a."""
+    B, T, d = 2, 300, 3
+    pl = V.resblock_plan(B, T, C, d, dt, True)
+    p, ref = R.case(B, T, d, dt, pl.tile_rows, 0, False)
+    q = _dev(p, cuda)
+    z = dict(q, ba=torch.zeros(C, device=cuda))
+    h0, y0 = _fused_fwd(z, d)
+    h1, y1 = _fused_fwd(q, d)
+    assert torch.equal(y1, y0) and torch.equal(h1, h0)
+    hu, yu = _unfused_fwd(z, d)
+    assert torch.equal(y1, yu) and torch.equal(h1, torch.relu(hu))
+    want_y = ref.r["y"]
+    assert float((y1.double().cpu() - want_y).abs().max()) <= (2.0 ** -7 if dt == torch.bfloat16 else 1e-5) * float(
+        want_y.abs().max())
+    dx0, g0 = _bwd_guarded(z, d)
+    dx1, g1 = _bwd_guarded(q, d)
+    assert torch.equal(dx1, dx0)
+    for k in R.GRADS:
+        assert torch.equal(g1[k], g0[k]), k
+    _assert_parity(_name(B, T, d, dt, " ba=None"), ref, dx1, g1)
+
+
+@pytest.mark.parametrize("dt", DTS, ids=DT_IDS)
+def test_exact_zeros_in_x(cuda, dt):
+    """x > 0, not x >= 0: at a planted zero (of either sign) dx is dy itself."""
+    B, T, d = 3, 300, 27
+    pl = V.resblock_plan(B, T, C, d, dt, True)
+    p, ref = R.case(B, T, d, dt, pl.tile_rows, 600, True)
+    zero = p["x"] == 0
+    assert int(zero.sum()) == 600 and bool(torch.signbit(p["x"][zero]).any())
+    dx, g = _bwd_guarded(_dev(p, cuda), d)
+    assert torch.equal(dx.cpu()[zero], p["dy"][zero])
+    _assert_parity(_name(B, T, d, dt, " zeros"), ref, dx, g)

@@ -948,14 +948,53 @@ static int bwd_rt_for(int d, int T) {
   return (d == 1 || d == 3 || d == 9) && T < 8192 ? 128 : bwd_rt_of(d);
 }
 
-static void plan(ResArgs& a, int per_cu, int rt, int min_tiles = 1) {
-  a.ntm = (a.T + rt - 1) / rt;
-  a.ntiles = a.ntm * a.B;
+static bool rs_model_dilation(int d) { return d == 1 || d == 3 || d == 9 || d == 27; }
+
+// What a forward or backward launch runs, settled on the host from the arguments alone: vqa_resblock_fwd and
+// vqa_resblock_bwd launch exactly this, and vqa_resblock_plan reports it without launching anything.
+struct ResPlan {
+  int rt, dt;                        // rows per tile; the compiled dilation (0: the runtime-dilation instance)
+  int ntm, ntiles, nwg, tpw, textra;  // workgroup w owns tiles [w tpw + min(w, textra), +tpw + (w < textra))
+  int parts;                         // weight-gradient partial rows per conv (backward: one per workgroup)
+  size_t lds, lds_max;               // the launch's dynamic LDS; the reservation raised on the kernel
+};
+
+static int rs_plan(const char* what, int B, int T, int C, int d, int dtype, bool backward, ResPlan& p) {
+  VQA_ARG(B > 0 && T > 0, "%s: bad arguments", what);
+  VQA_REQUIRE(vqa_resblock_supported(C, d, dtype), VQA_E_UNSUPPORTED, "%s: unsupported C=%d dilation=%d dtype=%d", what,
+              C, d, dtype);
+  VQA_ARG((long long)T * C * 4 < (1ll << 30), "%s: item too long for 32-bit buffer offsets (T=%d)", what, T);
+  const int esz = dtype == VQA_BF16 ? 2 : 4;
+  p.dt = rs_model_dilation(d) ? d : 0;
+  p.rt = backward ? bwd_rt_for(d, T) : fwd_rt_of(d);
+  // backward: at least kResMinTiles tiles per workgroup: a workgroup's weight-gradient partial row (2 x 3,104 fp32)
+  // is larger than a tile's activations, so short launches use fewer, longer-lived workgroups
+  const int per_cu = backward ? kResPerCU : 3, min_tiles = backward ? kResMinTiles : 1;
+  p.ntm = (T + p.rt - 1) / p.rt;
+  p.ntiles = p.ntm * B;
   // every slot gets floor(ntiles / nwg) tiles and the first (ntiles mod nwg) one more: workgroups w and
   // w + #CUs (dispatched to the same CU) never both hold an extra tile while extras <= #CUs
-  a.nwg = std::min(cu_count() * per_cu, std::max(1, a.ntiles / min_tiles));
-  a.tpw = a.ntiles / a.nwg;
-  a.textra = a.ntiles - a.tpw * a.nwg;
+  p.nwg = std::min(cu_count() * per_cu, std::max(1, p.ntiles / min_tiles));
+  p.tpw = p.ntiles / p.nwg;
+  p.textra = p.ntiles - p.tpw * p.nwg;
+  p.parts = backward ? p.nwg : 0;
+  // one LDS reservation for every dilation (the largest plan); the forward also launches with it
+  if (backward) {
+    p.lds = bwd_lds(d, esz, p.rt);
+    p.lds_max = bwd_lds(RMAXD, esz, RTM);
+    for (int dd : {1, 3, 9, 27}) p.lds_max = std::max(p.lds_max, bwd_lds(dd, esz, rs_bwd_rt(dd)));
+  } else {
+    p.lds = p.lds_max = std::max(fwd_lds(RMAXD, esz, RTM), fwd_lds(27, esz, rs_fwd_rt(27)));
+  }
+  return VQA_OK;
+}
+
+static void rs_apply(ResArgs& a, const ResPlan& p) {
+  a.ntm = p.ntm;
+  a.ntiles = p.ntiles;
+  a.tpw = p.tpw;
+  a.textra = p.textra;
+  a.nwg = p.nwg;
 }
 
 }  // namespace vqa
@@ -980,21 +1019,26 @@ extern "C" int vqa_resblock_fwd(const void* x, const float* wa, const float* ba,
                                 void* y, void* h_out, int B, int T, int C, int dilation, int dtype,
                                 vqa_stream_t stream) {
   VQA_ARG(x && wa && wb && y && B > 0 && T > 0, "resblock_fwd: bad arguments");
-  VQA_REQUIRE(vqa_resblock_supported(C, dilation, dtype), VQA_E_UNSUPPORTED,
-              "resblock_fwd: unsupported C=%d dilation=%d dtype=%d", C, dilation, dtype);
-  VQA_ARG((long long)T * C * 4 < (1ll << 30), "resblock_fwd: item too long for 32-bit buffer offsets (T=%d)", T);
+  ResPlan p;
+  if (int rc = rs_plan("resblock_fwd", B, T, C, dilation, dtype, false, p)) return rc;
   ResArgs a{x, nullptr, y, h_out, wa, ba, wb, bb, nullptr, nullptr, B, T, dilation, 0, 0, 0, 0, 0};
-  plan(a, 3, fwd_rt_of(dilation));
-  const int esz = dtype == VQA_BF16 ? 2 : 4;
-  // one LDS reservation for every dilation (the largest plan)
-  const size_t lds = std::max(fwd_lds(RMAXD, esz, RTM), fwd_lds(27, esz, rs_fwd_rt(27)));
+  rs_apply(a, p);
   const hipStream_t s = (hipStream_t)stream;
   const dim3 grid(a.nwg);
   const void* fn = dtype == VQA_BF16 ? rs_pick<RsFwd<bf16>>(dilation) : rs_pick<RsFwd<float>>(dilation);
-  if (int rc = raise_dyn_lds(fn, lds, "resblock_fwd_kernel")) return rc;
+  if (int rc = raise_dyn_lds(fn, p.lds_max, "resblock_fwd_kernel")) return rc;
   void* args[] = {&a};
-  (void)hipLaunchKernel(fn, grid, dim3(256), args, lds, s);
+  (void)hipLaunchKernel(fn, grid, dim3(256), args, p.lds, s);
   VQA_LAUNCHED("resblock_fwd_kernel");
+  return VQA_OK;
+}
+
+extern "C" int vqa_resblock_plan(int B, int T, int C, int dilation, int dtype, int backward,
+                                 vqa_resblock_plan_info* plan) {
+  VQA_ARG(plan, "resblock_plan: null plan");
+  ResPlan p;
+  if (int rc = rs_plan("resblock_plan", B, T, C, dilation, dtype, backward != 0, p)) return rc;
+  *plan = vqa_resblock_plan_info{p.rt, p.dt, p.ntm, p.ntiles, p.nwg, p.tpw, p.textra, p.parts, (int64_t)p.lds};
   return VQA_OK;
 }
 
@@ -1013,29 +1057,21 @@ extern "C" int vqa_resblock_bwd(const void* dy, const void* x, const float* wa, 
                                 vqa_partials_desc* desc, vqa_stream_t stream) {
   (void)bb;
   VQA_ARG(dy && x && wa && wb && dx && dwa && dwb && B > 0 && T > 0, "resblock_bwd: bad arguments");
-  VQA_ARG((long long)T * C * 4 < (1ll << 30), "resblock_bwd: item too long for 32-bit buffer offsets (T=%d)", T);
-  VQA_REQUIRE(vqa_resblock_supported(C, dilation, dtype), VQA_E_UNSUPPORTED,
-              "resblock_bwd: unsupported C=%d dilation=%d dtype=%d", C, dilation, dtype);
+  ResPlan p;
+  if (int rc = rs_plan("resblock_bwd", B, T, C, dilation, dtype, true, p)) return rc;
   const size_t need = vqa_resblock_bwd_workspace(B, T, C, dilation, dtype);
   VQA_ARG(workspace && ws_bytes >= need, "resblock_bwd: workspace %zu < %zu bytes", ws_bytes, need);
   const int E = 3 * RC * RC + RC;
   ResArgs a{x, dy, dx, nullptr, wa, ba, wb, nullptr, (float*)workspace, nullptr, B, T, dilation, 0, 0, 0, 0, 0};
-  // at least kResMinTiles tiles per workgroup: a workgroup's weight-gradient partial row (2 x 3,104 fp32) is
-  // larger than a tile's activations, so short launches use fewer, longer-lived workgroups
-  const int esz = dtype == VQA_BF16 ? 2 : 4;
   const hipStream_t s = (hipStream_t)stream;
-  const int rt = bwd_rt_for(dilation, T);
-  plan(a, kResPerCU, rt, kResMinTiles);
+  rs_apply(a, p);
   a.part_b = a.part_a + (size_t)a.nwg * E;
-  const size_t lds = bwd_lds(dilation, esz, rt);
-  size_t lds_max = bwd_lds(RMAXD, esz, RTM);  // one reservation for every dilation (the largest plan)
-  for (int dd : {1, 3, 9, 27}) lds_max = std::max(lds_max, bwd_lds(dd, esz, rs_bwd_rt(dd)));
-  const void* fn = rt != bwd_rt_of(dilation)
+  const void* fn = p.rt != bwd_rt_of(dilation)
                        ? (dtype == VQA_BF16 ? rs_pick<RsBwd128<bf16>>(dilation) : rs_pick<RsBwd128<float>>(dilation))
                        : (dtype == VQA_BF16 ? rs_pick<RsBwd<bf16>>(dilation) : rs_pick<RsBwd<float>>(dilation));
-  if (int rc = raise_dyn_lds(fn, lds_max, "resblock_bwd_kernel")) return rc;
+  if (int rc = raise_dyn_lds(fn, p.lds_max, "resblock_bwd_kernel")) return rc;
   void* args[] = {&a};
-  (void)hipLaunchKernel(fn, dim3(a.nwg), dim3(256), args, lds, s);
+  (void)hipLaunchKernel(fn, dim3(a.nwg), dim3(256), args, p.lds, s);
   VQA_LAUNCHED("resblock_bwd_kernel");
   const int nwg = a.nwg;
   const vqa_partials_desc da{a.part_a, dwa, dba, nwg, E, 3 * RC * RC, 0};

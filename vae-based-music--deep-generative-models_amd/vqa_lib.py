@@ -34,6 +34,7 @@ EXPORTED = [
     "vqa_spectral_loss", "vqa_spectral_loss_workspace", "vqa_stft_magnitude",
     "vqa_vq_argmin_split", "vqa_vq_split_bf16x3",
     "vqa_resblock_supported", "vqa_resblock_fwd", "vqa_resblock_bwd", "vqa_resblock_bwd_workspace",
+    "vqa_resblock_plan",
     "vqa_spectral_target_workspace", "vqa_spectral_target", "vqa_spectral_loss_target_workspace",
     "vqa_spectral_loss_target", "vqa_dtail_supported", "vqa_dtail_workspace", "vqa_dtail_fwd", "vqa_dtail_bwd",
     "vqa_step_metrics", "vqa_synthetic_batch",
@@ -115,6 +116,7 @@ _SIGS = {
     "vqa_resblock_fwd": (_I, [_P] * 7 + [_I] * 5 + [_P]),
     "vqa_resblock_bwd": (_I, [_P] * 11 + [_I] * 5 + [_P, _S, _P, _P]),
     "vqa_resblock_bwd_workspace": (_S, [_I] * 5),
+    "vqa_resblock_plan": (_I, [_I] * 6 + [_P]),
     "vqa_dtail_supported": (_I, [_I] * 7),
     "vqa_dtail_workspace": (_S, [_I] * 5),
     "vqa_dtail_fwd": (_I, [_P] * 6 + [_I] * 5 + [_P, _S, _P]),
@@ -359,6 +361,31 @@ def dtail_bwd(dy, h, w_up, b_up, w_out, b_out, dh, dw_up, db_up, dw_out, db_out)
 
 def resblock_supported(C, dilation, dtype) -> bool:
     return bool(lib().vqa_resblock_supported(C, dilation, dtype))
+
+
+class ResblockPlanInfo(ctypes.Structure):
+    """vqa_resblock_plan_info (include/vqa.h)."""
+    _fields_ = [("tile_rows", ctypes.c_int), ("compiled_dilation", ctypes.c_int), ("tiles_per_item", ctypes.c_int),
+                ("tiles", ctypes.c_int), ("workgroups", ctypes.c_int), ("tiles_per_workgroup", ctypes.c_int),
+                ("extra_tile_workgroups", ctypes.c_int), ("partial_rows", ctypes.c_int),
+                ("lds_bytes", ctypes.c_int64)]
+
+    def __repr__(self):
+        return "ResblockPlan(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+    def run(self, w):
+        """[first, end) tiles of workgroup w"""
+        first = w * self.tiles_per_workgroup + min(w, self.extra_tile_workgroups)
+        return first, first + self.tiles_per_workgroup + (w < self.extra_tile_workgroups)
+
+
+def resblock_plan(B, T, C, dilation, dtype, backward):
+    """vqa_resblock_plan: the ResblockPlanInfo a resblock_fwd / resblock_bwd call of these sizes follows (dtype a
+    torch dtype). Host-only, nothing is launched."""
+    r = ResblockPlanInfo()
+    _check(lib().vqa_resblock_plan(B, T, C, dilation, dtype_code(dtype), int(bool(backward)), ctypes.byref(r)),
+           "vqa_resblock_plan")
+    return r
 
 
 def resblock_fwd(x, wa, ba, wb, bb, y, dilation, h_out=None):
