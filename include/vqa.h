@@ -563,6 +563,22 @@ int vqa_attn_fwd(const void* q, const void* k, const void* v, void* o, float* ls
 int vqa_attn_bwd(const void* q, const void* k, const void* v, const void* o, const float* lse, const void* dout,
                  float* dsum, void* dq, void* dk, void* dv, int N, int T, int H, int head_dim, int l, int mode,
                  float scale, int dtype, vqa_stream_t stream);
+/* Attention probabilities of vqa_attn_fwd, recomputed from q, k and the lse it saved (log2 domain), fp32 out: the
+ * attention_weights of transformer.py:106-115, in the layouts keras MultiHeadAttention(return_attention_scores=True)
+ * gives factorized_attention.py:121-135, 260-284, 355-386 at a whole number of blocks. nb = T / l.
+ *   mode 0 (row)      w (N*nb, H, l, l):   w[n*nb+b][h][i][j] = j <= i ? p(q[b*l+i], k[b*l+j]) : 0
+ *   mode 2 (prev-row) w (N*nb, H, l, l):   b >= 1: p(q[b*l+i], k[(b-1)*l+j]); b == 0: 1/l (the zero block)
+ *   mode 1 (col)      w (N*l, H, nb, nb):  w[n*l+j][h][b][b'] = b' <= b ? p(q[b*l+j], k[b'*l+j]) : 0
+ * p(q, k) = 2^(q.k * scale * log2(e) - lse[query]): the scores are formed as the forward forms them, so the weights
+ * agree with the lse they are normalised by; bf16 inputs give fp32 weights from the fp32 accumulator. Masked
+ * entries are +0.0f; block 0 of mode 2 does not read lse (the forward's 0 there is a placeholder). Every element of
+ * w is written exactly once; only q, k and lse are read. Shape rules of vqa_attn_fwd (VQA_E_UNSUPPORTED: head_dim
+ * other than 16, modes 0/2 with l % 64 != 0, mode 1 with T/l > 8). VQA_E_INVALID_ARG before any launch (messages
+ * start "attn_weights:"): a null q, k, lse or w; a bad dtype or shape; a scale that is not finite and positive;
+ * w_elems other than vqa_attn_weights_elems(N, T, H, l, mode); w not 16-byte aligned. */
+size_t vqa_attn_weights_elems(int N, int T, int H, int l, int mode); /* host only; 0 on a bad shape */
+int vqa_attn_weights(const void* q, const void* k, const float* lse, float* w, size_t w_elems, int N, int T,
+                     int H, int head_dim, int l, int mode, float scale, int dtype, vqa_stream_t stream);
 /* Output head Dense(bins) fused with SparseCategoricalCrossentropy(from_logits) / accuracy
  * (autoregressive_fmha.py:80,158; autoregressive.py:189-212); logits are never written. wt = W^T (V, K) in
  * the activation dtype (vqa_head_wt). K = 128. head_fwd: per row lse, argmax (first maximum), and with

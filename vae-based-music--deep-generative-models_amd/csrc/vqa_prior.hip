@@ -1078,6 +1078,144 @@ __global__ __launch_bounds__(256) void attn_col_bwd_kernel(AttnArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Attention probabilities for inspection (transformer.py:106-115 attention_weights; the layouts keras
+// MultiHeadAttention(return_attention_scores=True) gives factorized_attention.py:121-135, 260-284, 355-386 at a
+// whole number of blocks): p = 2^(s*c - lse) recomputed from q, k and the lse the forward saved, fp32 out.
+// Store-bound (N*H*T*l floats for modes 0 / 2); every element of w is written exactly once, masked ones as +0.
+struct AttnWArgs {
+  const void* q;
+  const void* k;
+  const float* lse;
+  float* w;
+  int N, T, H, l;
+  float scale;
+  float uniform;  // 1.0f / l: every weight of mode 2's block 0 (identical bias keys)
+};
+
+constexpr int AWS = 64 + 4;  // LDS row stride (floats) of a wave's 16 x 64 probability tile
+
+// Modes 0 and 2, w (N*nb, H, l, l). The forward's tiling: a workgroup = 64 queries (wave w: 16), key tiles of 64
+// staged in LDS, S^T = K Q^T on the same MFMA, so a lane holds 4 consecutive keys of ONE query — a wave store of
+// the accumulator as it stands would be 16 rows x 64 B. The wave's 16 x 64 tile goes through its own LDS tile
+// instead and leaves as 4 instructions of 4 rows x 256 B (16 lanes x 16 B along each row); over the key loop a
+// wave writes its 16 output rows whole. Tiles past the diagonal (mode 0) and block 0 (mode 2) are constant fills
+// with the same map: no q, k or lse is read for them.
+template <class T, int MODE>
+__global__ __launch_bounds__(256) void attn_weights_kernel(AttnWArgs a) {
+  typedef Att<T> A;
+  __shared__ __attribute__((aligned(16))) T Ks[64 * AKS];
+  __shared__ __attribute__((aligned(16))) float Ps[4][16 * AWS];
+  const int qt = blockIdx.x, h = blockIdx.y, n = blockIdx.z, q0 = qt * 64, b = q0 / a.l;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), li = lane & 15, g = lane >> 4;
+  const int nt = a.l / 64;  // key tiles per output row
+  // the wave's 16 output rows: batch item n*nb + b, head h, rows q0 - b*l + 16*wave ..; 64-bit from here on
+  const long long blk = ((long long)n * (a.T / a.l) + b) * a.H + h;
+  float* wrow = a.w + (blk * a.l + (q0 - b * a.l + wave * 16)) * (long long)a.l;
+  const int sr = lane >> 4, sc = 4 * (lane & 15);  // store map: pass r writes row 4r + sr, columns sc .. sc+3
+  auto fill = [&](int t, float v) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) *(f32x4*)(wrow + (long long)(4 * r + sr) * a.l + t * 64 + sc) = f32x4{v, v, v, v};
+  };
+  if (MODE == 2 && b == 0) {  // the zero block: uniform weights; its lse is a placeholder and is not read
+    for (int t = 0; t < nt; ++t) fill(t, a.uniform);
+    return;
+  }
+  const long long qrow = (long long)n * a.T + q0 + wave * 16 + li;
+  const typename A::dfrag qf = A::ld_d((const T*)a.q + (qrow * a.H + h) * AHD);
+  const float lse = a.lse[qrow * a.H + h];
+  const int kt0 = MODE == 0 ? b * nt : (b - 1) * nt, tl = MODE == 0 ? qt - kt0 : nt - 1;  // last tile with scores
+  const float c = a.scale * kLog2e;
+  float* P = Ps[wave];
+  Chunk64<T> ck;
+  ck.load((const T*)a.k, (long long)n * a.T + kt0 * 64, a.H, h);
+  for (int t = 0; t <= tl; ++t) {
+    __syncthreads();
+    ck.store(Ks);
+    __syncthreads();
+    if (t < tl) ck.load((const T*)a.k, (long long)n * a.T + (kt0 + t + 1) * 64, a.H, h);
+#pragma unroll
+    for (int st = 0; st < 4; ++st) {
+      const f32x4 s = A::mm_d(A::ld_d(Ks + (st * 16 + li) * AKS), qf, f32x4{0.f, 0.f, 0.f, 0.f});
+      f32x4 p;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        p[i] = fexp2(__builtin_fmaf(s[i], c, -lse));
+        if (MODE == 0 && t == tl && st * 16 + 4 * g + i > wave * 16 + li) p[i] = 0.f;
+      }
+      *(f32x4*)(P + li * AWS + st * 16 + 4 * g) = p;
+    }
+    // the tile is the wave's own: a wave's LDS traffic is processed in order, the fences keep the compiler's order
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      *(f32x4*)(wrow + (long long)(4 * r + sr) * a.l + t * 64 + sc) = *(const f32x4*)(P + (4 * r + sr) * AWS + sc);
+    // the next tile's writes to P come after the loop's barriers
+  }
+  for (int t = tl + 1; t < nt; ++t) fill(t, 0.f);
+}
+
+// Mode 1, w (N*l, H, nb, nb): thread e = (n*l + j)*H + h of attn_col_fwd_kernel owns the nb x nb matrix at
+// w + e*nb*nb, so a workgroup's 256 matrices are one contiguous run that starts on a 16-byte boundary whatever nb
+// is. Rows of nb <= 8 floats cannot be 16-byte stores per thread (nb*nb is odd for odd nb): the matrices are
+// transposed through LDS and the workgroup streams the run out, lane f writing floats 4f .. 4f+3 (a wave: 1 KiB
+// contiguous); only the last workgroup can end in a tail of fewer than 4 floats. Scores as the column forward forms
+// them (the same sequential dot product), p = exp2(s*c - lse) as attn_col_bwd_kernel.
+template <class T, int NB>
+__global__ __launch_bounds__(256) void attn_col_weights_kernel(AttnWArgs a) {
+  constexpr int M = NB * NB;
+  __shared__ __attribute__((aligned(16))) float Ws[M * 256];  // [m][(t + m) & 255]: conflict-free both ways
+  const long long total = (long long)a.N * a.l * a.H, e0 = (long long)blockIdx.x * 256, e = e0 + threadIdx.x;
+  if (e < total) {
+    const int h = (int)(e % a.H), j = (int)((e / a.H) % a.l);
+    const long long n = e / ((long long)a.H * a.l);
+    auto off = [&](int b) { return (((long long)n * a.T + (long long)b * a.l + j) * a.H + h) * AHD; };
+    float kk[NB][AHD];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+      for (int d = 0; d < AHD; d += 4) {
+        const f32x4 v = ld4((const T*)a.k + off(b) + d);
+        kk[b][d] = v[0]; kk[b][d + 1] = v[1]; kk[b][d + 2] = v[2]; kk[b][d + 3] = v[3];
+      }
+    const float c = a.scale * kLog2e;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      float q[AHD];
+#pragma unroll
+      for (int d = 0; d < AHD; d += 4) {
+        const f32x4 v = ld4((const T*)a.q + off(b) + d);
+        q[d] = v[0]; q[d + 1] = v[1]; q[d + 2] = v[2]; q[d + 3] = v[3];
+      }
+      const float lse = a.lse[off(b) / AHD];
+#pragma unroll
+      for (int bb = 0; bb < NB; ++bb) {
+        float p = 0.f;
+        if (bb <= b) {
+          float s = 0.f;
+#pragma unroll
+          for (int d = 0; d < AHD; ++d) s += q[d] * kk[bb][d];
+          p = exp2f(s * c - lse);
+        }
+        const int m = b * NB + bb;
+        Ws[m * 256 + ((threadIdx.x + m) & 255)] = p;
+      }
+    }
+  }
+  __syncthreads();
+  const long long rest = total - e0;
+  const int cnt = (int)(rest < 256 ? rest : 256) * M;  // floats of this workgroup's run
+  float* out = a.w + e0 * M;
+  auto at = [&](int f) { const int t = f / M, m = f - t * M; return Ws[m * 256 + ((t + m) & 255)]; };
+  for (int f = threadIdx.x * 4; f < cnt; f += 1024) {
+    if (f + 4 <= cnt) *(f32x4*)(out + f) = f32x4{at(f), at(f + 1), at(f + 2), at(f + 3)};
+    else
+      for (int u = f; u < cnt; ++u) out[u] = at(u);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Output head fused with the loss (autoregressive_fmha.py:80,158 Dense(bins); autoregressive.py:189-212):
 // logits = X W + b are never written. Wt = W^T in the activation dtype, (V, 128), prepared once per step.
 //   head_fwd:    per row lse, argmax (first maximum, tf.argmax), and with targets the row loss lse - logit[t]
@@ -2291,6 +2429,56 @@ extern "C" int vqa_attn_bwd(const void* q, const void* k, const void* v, const v
   AttnArgs a{q, k, v, (void*)o, (float*)lse, dout, dsum, dq, dk, dv, nullptr, N, T, H, l, scale};
   hipStream_t s = (hipStream_t)stream;
   return dtype == VQA_BF16 ? launch_attn<bf16>(false, mode, a, s) : launch_attn<float>(false, mode, a, s);
+}
+
+extern "C" size_t vqa_attn_weights_elems(int N, int T, int H, int l, int mode) {
+  if (!(N > 0 && T > 0 && H > 0 && l > 0 && T % l == 0 && mode >= 0 && mode <= 2)) return 0;
+  const size_t nb = (size_t)(T / l), side = mode == 1 ? nb : (size_t)l, items = mode == 1 ? (size_t)l : nb;
+  size_t e = 0;  // N * items * H * side * side
+  if (__builtin_mul_overflow((size_t)N, items, &e) || __builtin_mul_overflow(e, (size_t)H, &e) ||
+      __builtin_mul_overflow(e, side, &e) || __builtin_mul_overflow(e, side, &e))
+    return 0;
+  return e;
+}
+
+template <class T>
+static int launch_attn_weights(int mode, const AttnWArgs& a, hipStream_t s) {
+  if (mode == 1) {
+    const unsigned g = (unsigned)(((long long)a.N * a.l * a.H + 255) / 256);
+#define VQA_COLW(NB) \
+  case NB: hipLaunchKernelGGL((attn_col_weights_kernel<T, NB>), dim3(g), dim3(256), 0, s, a); break;
+    switch (a.T / a.l) { VQA_COLW(1) VQA_COLW(2) VQA_COLW(3) VQA_COLW(4) VQA_COLW(5) VQA_COLW(6) VQA_COLW(7) VQA_COLW(8) }
+#undef VQA_COLW
+    VQA_LAUNCHED("attn_col_weights_kernel");
+    return VQA_OK;
+  }
+  const dim3 grid(a.T / 64, a.H, a.N);
+  if (mode == 0) hipLaunchKernelGGL((attn_weights_kernel<T, 0>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_weights_kernel<T, 2>), grid, dim3(256), 0, s, a);
+  VQA_LAUNCHED("attn_weights_kernel");
+  return VQA_OK;
+}
+
+extern "C" int vqa_attn_weights(const void* q, const void* k, const float* lse, float* w, size_t w_elems, int N, int T,
+                                int H, int head_dim, int l, int mode, float scale, int dtype, vqa_stream_t stream) {
+  VQA_ARG(q && k && lse && w, "attn_weights: null q, k, lse or w");
+  VQA_ARG(pr_dt(dtype), "attn_weights: dtype %d is neither VQA_F32 nor VQA_BF16", dtype);
+  VQA_ARG(N > 0 && T > 0 && H > 0 && l > 0 && T % l == 0 && mode >= 0 && mode <= 2,
+          "attn_weights: bad shape (N %d, T %d, H %d, l %d, mode %d)", N, T, H, l, mode);
+  VQA_REQUIRE(head_dim == AHD, VQA_E_UNSUPPORTED, "attn_weights: head_dim %d unsupported (16)", head_dim);
+  VQA_REQUIRE(mode == 1 || l % 64 == 0, VQA_E_UNSUPPORTED, "attn_weights: block length %d not a multiple of 64", l);
+  VQA_REQUIRE(mode != 1 || T / l <= 8, VQA_E_UNSUPPORTED,
+              "attn_weights: column attention supports 1..8 blocks (got %d)", T / l);
+  VQA_ARG(std::isfinite(scale) && scale > 0.f, "attn_weights: scale %g is not finite and positive", (double)scale);
+  const size_t want = vqa_attn_weights_elems(N, T, H, l, mode);
+  VQA_ARG(want != 0 && w_elems == want, "attn_weights: w holds %zu elements, the layout of mode %d has %zu", w_elems,
+          mode, want);
+  VQA_ARG((reinterpret_cast<uintptr_t>(w) & 15) == 0, "attn_weights: w is not 16-byte aligned");
+  VQA_ARG(mode == 1 ? ((long long)N * l * H + 255) / 256 <= 0x7fffffffLL : (N <= 65535 && H <= 65535),
+          "attn_weights: N %d or H %d beyond the launch grid", N, H);
+  AttnWArgs a{q, k, lse, w, N, T, H, l, scale, 1.0f / (float)l};
+  hipStream_t s = (hipStream_t)stream;
+  return dtype == VQA_BF16 ? launch_attn_weights<bf16>(mode, a, s) : launch_attn_weights<float>(mode, a, s);
 }
 
 extern "C" int vqa_head_wt(const float* w, void* wt, int K, int V, int dtype, vqa_stream_t stream) {

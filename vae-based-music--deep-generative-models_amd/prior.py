@@ -58,6 +58,38 @@ def positional_encoding(position, d_model):
 ATTN_NAMES = {0: "row", 1: "col", 2: "prev row"}
 
 
+def dense_attention(w, attn_type, block_len, n_samples):
+    """A factorized attention-weight tensor ('transformer_layer_{i}_attention') scattered into the dense causal map
+    (n_samples, H, T, T), zero wherever the layer does not attend — what a head-by-head plot shows
+    (utils/tf_utils.py:42-67). attn_type 0 / 'row': w (N*nb, H, l, l); 1 / 'col': w (N*l, H, nb, nb); 2 / 'prev row':
+    as row, block b's keys being block b-1 (block 0 attends the zero block, which is no position of the sequence:
+    its rows stay zero). Index arithmetic only, on w's device (CPU tensors too)."""
+    mode = attn_type if attn_type in ATTN_NAMES else {v: k for k, v in ATTN_NAMES.items()}.get(attn_type)
+    if mode is None:
+        raise ValueError(f"attn_type {attn_type!r}: one of {sorted(ATTN_NAMES)} or {sorted(ATTN_NAMES.values())}")
+    N, l = int(n_samples), int(block_len)
+    if w.dim() != 4 or N <= 0 or l <= 0 or w.shape[0] % N:
+        raise ValueError(f"weights of shape {tuple(w.shape)} do not hold {N} samples")
+    H = w.shape[1]
+    if mode == 1:
+        nb = w.shape[2]
+        if w.shape[0] != N * l or w.shape[3] != nb:
+            raise ValueError(f"column weights of shape {tuple(w.shape)}: expected ({N * l}, H, nb, nb)")
+    else:
+        nb = w.shape[0] // N
+        if tuple(w.shape[2:]) != (l, l):
+            raise ValueError(f"{ATTN_NAMES[mode]} weights of shape {tuple(w.shape)}: expected (N*nb, H, {l}, {l})")
+    out = w.new_zeros(N, H, nb, l, nb, l)  # [n, h, query block, query position, key block, key position]
+    if mode == 1:
+        # out[n, h, b, j, b', j] = w[n*l + j, h, b, b']
+        out.diagonal(dim1=3, dim2=5).copy_(w.reshape(N, l, H, nb, nb).permute(0, 2, 3, 4, 1))
+    else:
+        w5 = w.reshape(N, nb, H, l, l)
+        for b in range(mode // 2, nb):
+            out[:, :, b, :, b - mode // 2, :] = w5[:, b]
+    return out.reshape(N, H, nb * l, nb * l)
+
+
 class FactorizedAttention:
     def __init__(self, ctc_len, num_heads, d_model, blocks, attn_func=0, m_attn=0.25, drop_out_rate=0.0, **kwargs):
         self.width = int(d_model * m_attn)
@@ -132,10 +164,12 @@ class ResidualAttnBlock:
         return out
 
     # -------------------------------------------------------------- forward / backward on the device
-    def forward(self, x, T, training, save, seed, salt, counter=None, row0=0):
+    def forward(self, x, T, training, save, seed, salt, counter=None, row0=0, weights_out=None):
         """x (N, T, d) -> (N, T, d). save: keep what backward needs (layer input, qkv, heads, lse, o32, x1).
         row0: the global index of x's first (sequence, position) row — the dropout mask's key under data
-        parallelism (rank * N * T), so every rank draws its slice of the single-process mask."""
+        parallelism (rank * N * T), so every rank draws its slice of the single-process mask.
+        weights_out: a list that receives this layer's attention probabilities (V.attn_weights on the layer's own
+        q, k and lse: one more launch, fp32 in the reference's factorized layout); None launches nothing more."""
         f, cdt, eps = self.fmha, x.dtype, 1e-6
         N = x.shape[0]
         w = f.width
@@ -159,6 +193,9 @@ class ResidualAttnBlock:
         lse = torch.empty(N, T, f.num_heads, dtype=torch.float32, device=x.device)
         V.attn_fwd(qh, kh, vh, oh, lse, f.attn_func, f.block_len, f.num_heads, 1.0 / math.sqrt(f.head_dim),
                    vbias=f.p("mha/value/bias"))
+        if weights_out is not None:
+            weights_out.append(V.attn_weights(qh, kh, lse, f.attn_func, f.block_len, f.num_heads,
+                                              1.0 / math.sqrt(f.head_dim)))
         o32 = torch.empty_like(qh)
         V.seqlin_fwd_prepped(oh, wp["out"], f.p("mha/out/bias"), o32, T)
         x1 = torch.empty_like(x)
@@ -353,9 +390,11 @@ class FMHABasedAutoregressiveModel:
         V.seqlin_prep(descs, self.cdt)
 
     def hidden(self, tokens, training=False, x_cond=None, y_cond=None, save=False, seed=0, counter=None,
-               prepped=False, row0=0):
+               prepped=False, row0=0, attn_weights=None):
         """Embedding + transformer: (N, T) tokens -> (N, T, d) final hidden state (the head's input). row0: the
-        global index of the first (sequence, position) row (data parallel: rank * N * T) — the dropout masks' key."""
+        global index of the first (sequence, position) row (data parallel: rank * N * T) — the dropout masks' key.
+        attn_weights: (layer indices, dict) — the dict receives 'transformer_layer_{i}_attention' of those layers
+        (transformer.py:106-115); None: no layer computes its weights."""
         if not prepped:
             self.prep_weights(bwd=False)
         tokens = tokens.contiguous()
@@ -371,9 +410,24 @@ class FMHABasedAutoregressiveModel:
         if y_cond is not None and tuple(y_cond.shape) != (N, self.d_model):
             raise ValueError(f"y_cond shape {tuple(y_cond.shape)}: expected ({N}, {self.d_model})")
         x = self._embed(tokens, training, x_cond, y_cond, seed, counter, row0)
+        want, got = attn_weights if attn_weights is not None else ((), None)
         for i, ly in enumerate(self.transformer.layers):
-            x = ly.forward(x, T, training, save, seed, 1000 + i, counter, row0)
+            wo = [] if i in want else None
+            x = ly.forward(x, T, training, save, seed, 1000 + i, counter, row0, weights_out=wo)
+            if wo is not None:
+                got[f"transformer_layer_{i}_attention"] = wo[0]
         return x
+
+    def _weight_layers(self, sel):
+        """return_attention_weights -> the layer indices it asks for: False none, True all, else an iterable of
+        indices (ValueError outside [0, depth))."""
+        if sel is None or isinstance(sel, (bool, np.bool_)):
+            return tuple(range(self.depth)) if sel else ()
+        idx = tuple(int(i) for i in sel)
+        for i in idx:
+            if not 0 <= i < self.depth:
+                raise ValueError(f"return_attention_weights: layer {i} outside [0, {self.depth})")
+        return idx
 
     def _cond(self, x_cond, save=False):
         if x_cond is None:
@@ -384,27 +438,39 @@ class FMHABasedAutoregressiveModel:
         return self.conditioner.forward(x_cond.long().contiguous(), save=save)
 
     # -------------------------------------------------------------- Keras-like call / sample
-    def __call__(self, x, training=False, x_cond=None, y_cond=None):
-        """autoregressive_fmha.py:109-160 -> ((N, T, bins) fp32 logits, {}). Logits are materialised here (the
-        training step never does): 128-wide vocab slices of the head as sequence-linear launches."""
+    def __call__(self, x, training=False, x_cond=None, y_cond=None, return_attention_weights=False):
+        """autoregressive_fmha.py:109-160 -> ((N, T, bins) fp32 logits, attention weights). Logits are materialised
+        here (the training step never does): 128-wide vocab slices of the head as sequence-linear launches.
+        return_attention_weights: False -> {}; True -> {'transformer_layer_{i}_attention': fp32 device tensor} of
+        every layer (transformer.py:106-115), an iterable of layer indices -> of those layers only. Row and
+        previous-row layers give (N*blocks, H, l, l), column layers (N*l, H, blocks, blocks), as keras
+        MultiHeadAttention returns them to the reference (N*H*T*l floats per row layer: opt-in, per layer)."""
         tokens = torch.as_tensor(x, device=self.device).long()
+        want = self._weight_layers(return_attention_weights)
+        weights = {}
         with torch.no_grad():
-            h = self.hidden(tokens, training, self._cond(x_cond), self._ycond(y_cond))
-            N, T = tokens.shape
-            # the vocabulary zero-padded to a multiple of 16 (the sequence-linear kernel's output tile)
-            Vp = -(-self.bins // 16) * 16
-            wt32 = torch.zeros(Vp, self.d_model, dtype=torch.float32, device=self.device)
-            V.head_wt(self.store.view(self.out_kernel), wt32[:self.bins])
-            hf = h.float().contiguous()
-            logits = torch.empty(N, T, Vp, dtype=torch.float32, device=self.device)
-            b = torch.zeros(Vp, dtype=torch.float32, device=self.device)
-            b[:self.bins] = self.store.view(self.out_bias)
-            for v0 in range(0, Vp, 128):
-                n = min(128, Vp - v0)
-                V.seqlin_fwd(hf, wt32[v0:v0 + n], b[v0:v0 + n], logits[..., v0:v0 + n], T, wtrans=True)
-        return (logits[..., :self.bins].contiguous() if Vp != self.bins else logits), {}
+            h = self.hidden(tokens, training, self._cond(x_cond), self._ycond(y_cond),
+                            attn_weights=(want, weights) if want else None)
+            logits = self._logits(h)
+        return logits, weights
 
     call = __call__
+
+    def _logits(self, h):
+        """(N, T, d) final hidden state -> the materialised (N, T, bins) fp32 logits."""
+        N, T = h.shape[:2]
+        # the vocabulary zero-padded to a multiple of 16 (the sequence-linear kernel's output tile)
+        Vp = -(-self.bins // 16) * 16
+        wt32 = torch.zeros(Vp, self.d_model, dtype=torch.float32, device=self.device)
+        V.head_wt(self.store.view(self.out_kernel), wt32[:self.bins])
+        hf = h.float().contiguous()
+        logits = torch.empty(N, T, Vp, dtype=torch.float32, device=self.device)
+        b = torch.zeros(Vp, dtype=torch.float32, device=self.device)
+        b[:self.bins] = self.store.view(self.out_bias)
+        for v0 in range(0, Vp, 128):
+            n = min(128, Vp - v0)
+            V.seqlin_fwd(hf, wt32[v0:v0 + n], b[v0:v0 + n], logits[..., v0:v0 + n], T, wtrans=True)
+        return logits[..., :self.bins].contiguous() if Vp != self.bins else logits
 
     def _ycond(self, y_cond, n=None):
         """(N, d_model) fp32 label embeddings for position 0 (label_conditioners.py:26-45 gives (N, 1, d_model));
@@ -429,10 +495,17 @@ class FMHABasedAutoregressiveModel:
         next token = argmax(logits / temperature + Gumbel noise) over the top_k largest logits (0: all). One
         persistent decode launch. prime (N, P <= max_length) int64: the tokens after the start token that are
         given, not drawn (the codes a window of long-form sampling shares with the windows before it); the noise
-        is keyed by the absolute step, so a prime taken from an unprimed draw of the same seed reproduces it."""
+        is keyed by the absolute step, so a prime taken from an unprimed draw of the same seed reproduces it.
+        return_attention_weights (True, or layer indices): returns (tokens, weights) with the weights of
+        self(tokens[:, :-1], ...) on the drawn tokens (autoregressive_fmha.py:236-238); max_length must then be a
+        whole number of blocks."""
         L = self.context_length if max_length is None else int(max_length)
         if not 0 < L <= self.context_length:
             raise ValueError(f"max_length {L} outside (0, {self.context_length}]")
+        want = self._weight_layers(return_attention_weights)
+        if want and L % (self.context_length // self.blocks):
+            raise ValueError(f"return_attention_weights: max_length {L} is not a whole number of blocks of "
+                             f"{self.context_length // self.blocks} (a partial trailing block has no weight layout)")
         temperature = float(temperature)
         if not (math.isfinite(temperature) and temperature > 0.0):
             raise ValueError(f"temperature {temperature} must be finite and > 0")
@@ -490,8 +563,10 @@ class FMHABasedAutoregressiveModel:
                        prime=prime, temperature=temperature, top_k=top_k)
         if return_logits:
             return tokens, logits
-        if return_attention_weights:
-            return tokens, {}  # the decode kernel keeps no attention-weight tensors
+        if want:
+            # the decode kernel keeps no attention-weight tensors: one more forward over the drawn tokens
+            _, weights = self(tokens[:, :-1], x_cond=x_cond, y_cond=y_cond, return_attention_weights=want)
+            return tokens, weights
         return tokens
 
     def sequence_loss(self, inputs, targets, x_cond=None, y_cond=None, loss_fn=None):
@@ -840,6 +915,40 @@ class Prior:
         self.train_loss_tracker.update_state(out[0])
         self.train_accuracy_tracker.update_state(out[1])
         return self.results()
+
+    def __call__(self, inputs, return_attention_weights=False, logits=True):
+        """prior.py:200-238 Prior.call, the inspection pass of PriorMonitor.on_epoch_end (src/callback/
+        monitors.py:94-104): the model on latent_input = [start, codes[:-1]] with training=False, label and
+        upper-level conditioning as test_step. inputs: anything `_codes` takes except a feed. Returns (pred_logits,
+        target, attn_weights, loss, accuracy): pred_logits the materialised (N, T, bins) fp32 logits, or with
+        logits=False the fused head's (N, T) int64 argmax (all the monitor takes of them; skips the N*T*bins tensor);
+        target the codes; attn_weights as FMHABasedAutoregressiveModel.__call__(return_attention_weights=...); loss and
+        accuracy 0-d device tensors, the fused head's mean row loss and mean correctness. No tracker, optimizer or
+        step state is touched."""
+        if isinstance(inputs, CodeFeed):
+            raise ValueError("Prior.__call__ takes audio or codes, not a feed (it would consume a batch)")
+        m = self.prior
+        want = m._weight_layers(return_attention_weights)
+        codes, upper, y = self._codes(inputs)
+        N, T = codes.shape
+        M = N * T
+        weights = {}
+        with torch.no_grad():
+            latent = torch.empty_like(codes)
+            V.tf_mix(codes, None, None, latent, m.start_token)
+            h = m.hidden(latent, False, m._cond(upper), self._label_embed(y),
+                         attn_weights=(want, weights) if want else None)
+            pred = m._logits(h) if logits else torch.empty(N, T, dtype=torch.int64, device=self.device)
+            lse = torch.empty(M, dtype=torch.float32, device=self.device)
+            lr, cr = torch.empty_like(lse), torch.empty_like(lse)
+            V.head_fwd(h, m._wt(m.cdt), m.store.view(m.out_bias), lse, amax=None if logits else pred, targets=codes,
+                       loss_row=lr, correct=cr)
+            out = torch.empty(2, dtype=torch.float32, device=self.device)
+            V.rowsum(lr, 1, M, 1.0 / M, out[0:1])
+            V.rowsum(cr, 1, M, 1.0 / M, out[1:2])
+        return pred, codes, weights, out[0], out[1]
+
+    call = __call__
 
     def evaluate(self, x=None, y=None, batch_size=None, verbose=0, steps=None, return_dict=False, **kwargs):
         """keras Model.evaluate over test_step (prior.py:337-372), as src/callback/monitors.py:81 calls it on the

@@ -47,6 +47,7 @@ EXPORTED = [
     "vqa_prior_decode", "vqa_prior_decode_primed",
     "vqa_corpus_steps_per_epoch", "vqa_corpus_batch", "vqa_pcm_encode", "vqa_code_batch",
     "vqa_resample", "vqa_resample_route",
+    "vqa_attn_weights_elems", "vqa_attn_weights",
 ]
 
 
@@ -143,6 +144,8 @@ _SIGS = {
     "vqa_tf_mix": (_I, [_P, _P, _P, _P, _I, _I, _L, _F, _U, _U, _L, _P, _P]),
     "vqa_attn_fwd": (_I, [_P] * 6 + [_I] * 6 + [_F, _I, _P]),
     "vqa_attn_bwd": (_I, [_P] * 10 + [_I] * 6 + [_F, _I, _P]),
+    "vqa_attn_weights_elems": (_S, [_I] * 5),
+    "vqa_attn_weights": (_I, [_P] * 4 + [_S] + [_I] * 6 + [_F, _I, _P]),
     "vqa_head_wt": (_I, [_P, _P, _I, _I, _I, _P]),
     "vqa_head_fwd": (_I, [_P] * 8 + [_L, _I, _I, _I, _P]),
     "vqa_head_bwd_workspace": (_S, [_L, _I, _I]),
@@ -955,6 +958,48 @@ def attn_bwd(q, k, v, o, lse, dout, dsum, dq, dk, dv, mode, l, heads, scale):
     _check(lib().vqa_attn_bwd(ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), ptr(dout), ptr(dsum), ptr(dq), ptr(dk),
                               ptr(dv), N, T, heads, C // heads, l, mode, scale, dtype_code(q.dtype), stream()),
            "vqa_attn_bwd")
+
+
+def attn_weights_shape(N, T, H, l, mode):
+    """The shape of vqa_attn_weights' output (include/vqa.h): (N*nb, H, l, l) for row (0) and previous-row (2)
+    layers, (N*l, H, nb, nb) for column (1) layers, nb = T / l. Host-only."""
+    N, T, H, l, mode = int(N), int(T), int(H), int(l), int(mode)
+    if not (N > 0 and T > 0 and H > 0 and l > 0 and T % l == 0 and mode in (0, 1, 2)):
+        raise VQAError(f"attn_weights: bad shape (N {N}, T {T}, H {H}, l {l}, mode {mode})")
+    nb = T // l
+    return (N * l, H, nb, nb) if mode == 1 else (N * nb, H, l, l)
+
+
+def attn_weights(q, k, lse, mode, l, heads, scale, out=None):
+    """Attention probabilities of attn_fwd on the same q, k (N, T, H*16) and the lse (N, T, H) it saved
+    (vqa_attn_weights, include/vqa.h): an fp32 tensor of attn_weights_shape(N, T, H, l, mode), allocated here or the
+    `out` given. Everything is checked on the host before the call."""
+    if q.dtype not in (torch.float32, torch.bfloat16) or k.dtype != q.dtype:
+        raise VQAError(f"attn_weights: q and k are both float32 or both bfloat16 (got {q.dtype}, {k.dtype})")
+    if lse.dtype != torch.float32:
+        raise VQAError(f"attn_weights: lse is float32 (got {lse.dtype})")
+    heads = int(heads)
+    if q.dim() != 3 or k.shape != q.shape or heads <= 0 or q.shape[2] % heads:
+        raise VQAError(f"attn_weights: q and k are (N, T, H*head_dim) (got {tuple(q.shape)}, {tuple(k.shape)}, "
+                       f"{heads} heads)")
+    N, T, C = q.shape
+    if tuple(lse.shape) != (N, T, heads):
+        raise VQAError(f"attn_weights: lse is ({N}, {T}, {heads}) (got {tuple(lse.shape)})")
+    shape = attn_weights_shape(N, T, heads, l, mode)
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != shape):
+        raise VQAError(f"attn_weights: out is float32 {shape} (got {out.dtype} {tuple(out.shape)})")
+    for name, t in (("q", q), ("k", k), ("lse", lse)) + ((("out", out),) if out is not None else ()):
+        if not t.is_cuda:
+            raise VQAError(f"attn_weights: {name} is a CPU tensor (device tensors only)")
+        if not t.is_contiguous():
+            raise VQAError(f"attn_weights: {name} is not contiguous (strides {t.stride()})")
+        if t.device != q.device:
+            raise VQAError(f"attn_weights: {name} is on {t.device}, q on {q.device}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=q.device)
+    _check(lib().vqa_attn_weights(ptr(q), ptr(k), ptr(lse), ptr(out), out.numel(), N, T, heads, C // heads, int(l),
+                                  int(mode), float(scale), dtype_code(q.dtype), stream()), "vqa_attn_weights")
+    return out
 
 
 def head_wt(w, wt):
