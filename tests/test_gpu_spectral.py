@@ -3,11 +3,18 @@
 Follows data_utils.py:25-40 (spectral / norm) and vqvae.py:309-326 (_multispectral_loss); the oracle's
 gradient is torch autograd through rfft/abs (abs'(0) = 0, as TF). Tolerances (fp32 FFT vs fp64):
 magnitudes 2e-6 of the spectrum's max, loss 1e-5 relative, gradient 1e-4 of its max-abs.
+
+test_single_resolution and below use white noise (tests/dtail_parity_ref.white_signals: no bin and no sample
+dominates, so the same three bounds bind on every bin and every sample) and take one resolution at a time, so each
+of the three FFT implementations (the frame kernel, the Stockham pair kernel for 256 / 512 / 1024, the four-step pair
+kernel for 2048) is held to the bounds alone in each of its modes, at every frame geometry the layout accepts, with
+either gather kernel, down to one frame per item, and on every item of a persistent walk of three pairs per wave.
 """
 import numpy as np
 import pytest
 import torch
 
+import dtail_parity_ref as D
 import vqa_lib as V
 from data_utils import STFT_ARGS, SpectralTarget, multispectral_loss_and_grad, spectral
 from oracle import vqvae_ref as R
@@ -167,3 +174,113 @@ def test_pair_magnitudes_vs_oracle(cuda, B, T):
         assert got.shape == ref.shape, (got.shape, ref.shape)
         err = (got - ref).abs().max() / ref.abs().max()
         assert err < 2e-6, (n_fft, float(err))
+
+
+# ------------------------------------------------------------------ one resolution at a time, white noise
+def _target_mags(xd, B, T, n_fft, hop, win):
+    """|S_x| as vqa_spectral_target leaves it (the pair kernel's magnitude mode), read by the buffer's layout"""
+    buf = V.spectral_target(xd, [n_fft], [hop], [win]).view(torch.float32).cpu()
+    al = lambda n: (n + 63) // 64 * 64  # noqa: E731
+    F, KB = 1 + (T - win) // hop, n_fft // 2 + 1
+    o = al(2 * n_fft) + al(win)
+    return buf[o:o + B * F * KB].double().reshape(B, F, KB)
+
+
+def _loss_grad(xd, rd, res, copies, grad=True):
+    B, T = xd.shape
+    a = [[v] * copies for v in res]
+    out, item = torch.full((1,), float("nan"), device=xd.device), torch.full((B,), float("nan"), device=xd.device)
+    dr = torch.full((B + 2, T), float("nan"), device=xd.device) if grad else None     # one guard item either side
+    ws = V.workspace(V.spectral_loss_workspace(B, T, *a, with_grad=grad), xd.device)
+    V.spectral_loss(xd, rd, out, dr[1:B + 1] if grad else None, item, *a, ws=ws)
+    torch.cuda.synchronize()
+    if grad:
+        assert bool(torch.isnan(dr[[0, B + 1]]).all()), "gradient written outside its items"
+        dr = dr[1:B + 1].cpu()
+    return out.cpu(), item.cpu(), dr
+
+
+def _single(cuda, B, T, n_fft, hop, win, tag):
+    """every mode of one resolution against the fp64 oracle; returns the figures"""
+    x, r = D.white_signals(B, T, seed=n_fft + 7 * hop + win + B)
+    m_ref, item_ref, loss_ref, g_ref = D.spectral_oracle(x, r, n_fft, hop, win)
+    xd, rd = x.to(cuda).contiguous(), r.to(cuda).contiguous()
+    F, KB = 1 + (T - win) // hop, n_fft // 2 + 1
+    smax = m_ref.abs().max()
+    # magnitude mode of the pair kernel, and the frame kernel
+    e_pair = float((_target_mags(xd, B, T, n_fft, hop, win) - m_ref).abs().max() / smax)
+    fm = torch.full((B, F, KB), float("nan"), device=cuda)
+    V.stft_magnitude(xd, fm, n_fft, hop, win)
+    e_frame = float((fm.cpu().double() - m_ref).abs().max() / smax)
+    # gradient mode (the 8-frame gather while <= 8 frames cover a sample) and loss-only mode
+    loss, item, g = _loss_grad(xd, rd, (n_fft, hop, win), 1)
+    e_loss = abs(float(loss) - loss_ref) / loss_ref
+    e_item = float(((item.double() - item_ref).abs() / item_ref).max())
+    e_grad = float((g.double() - g_ref).abs().max() / g_ref.abs().max())
+    loss0, item0, _ = _loss_grad(xd, rd, (n_fft, hop, win), 1, grad=False)
+    print(f"PARITY spectral {tag} n_fft={n_fft} hop={hop} win={win} B={B} T={T} F={F} magnitudes pair {e_pair:.2e} "
+          f"frame {e_frame:.2e} (bound {D.SPEC_MAG:.0e}) loss {e_loss:.2e} item {e_item:.2e} (bound {D.SPEC_LOSS:.0e}) "
+          f"gradient {e_grad:.2e} (bound {D.SPEC_GRAD:.0e})")
+    assert e_pair < D.SPEC_MAG and e_frame < D.SPEC_MAG, (e_pair, e_frame)
+    assert e_loss < D.SPEC_LOSS and e_item < D.SPEC_LOSS, (e_loss, e_item)
+    assert e_grad < D.SPEC_GRAD, e_grad
+    assert torch.equal(loss0.view(torch.int32), loss.view(torch.int32)) and torch.equal(item0, item)
+    # samples no frame covers (between frames when hop > win; past the last frame): an exact zero
+    gap = D.uncovered(T, hop, win)
+    assert (hop > win) == bool(gap[:(F - 1) * hop + win].any())
+    assert torch.count_nonzero(g[:, gap]).item() == 0
+    return xd, rd, g, loss_ref, g_ref
+
+
+def _five_copies(xd, rd, res, g, loss_ref, g_ref):
+    """the same resolution five times: more than kGatherMaxRes = 4 forces spec_gather_kernel, and the five equal
+    terms average to the same loss. Both gathers sum a sample's frames in the same order, so the sums agree to the
+    bit; the scale they are multiplied by does not (1 / (5 B) for 1 / B, rounded once each, and five products
+    added), which is worth at most 12 roundings of 2^-24 with no cancellation (five equal terms): every element
+    within 16 x 2^-24 of its own size, zeros exact."""
+    loss5, _, g5 = _loss_grad(xd, rd, res, 5)
+    assert abs(float(loss5) - loss_ref) / loss_ref < D.SPEC_LOSS
+    assert float((g5.double() - g_ref).abs().max() / g_ref.abs().max()) < D.SPEC_GRAD
+    assert bool(((g5.double() - g.double()).abs() <= 16 * 2.0 ** -24 * g.double().abs()).all())
+    assert torch.equal(g5 == 0, g == 0)
+
+
+def _geometries(n_fft):
+    win = (n_fft * 5 // 8) | 1                       # odd, < n_fft: 161, 321, 641, 1281
+    return [(n_fft // 4, n_fft), (win // 5 + 1, win), (win, win), (win + 13, win)]
+
+
+@pytest.mark.parametrize("n_fft,hop,win", [(n, h, w) for n in (256, 512, 1024, 2048) for h, w in _geometries(n)])
+def test_single_resolution(cuda, n_fft, hop, win):
+    """full window without zero padding; an odd window; hop == win; hop > win (gaps between the frames)"""
+    B, T = 3, 3 * n_fft + 37
+    assert (win + hop - 1) // hop <= 8                # alone: spec_gather8_kernel (kGatherMaxF)
+    xd, rd, g, loss_ref, g_ref = _single(cuda, B, T, n_fft, hop, win, "single")
+    _five_copies(xd, rd, (n_fft, hop, win), g, loss_ref, g_ref)
+
+
+@pytest.mark.parametrize("B,T,F", [(1, 300, 1), (4, 300, 1), (3, 400, 2), (2, 500, 3)])
+def test_frame_count_edges(cuda, B, T, F):
+    """F = 1 with B = 1: a lone half pair; F = 1 with B = 4: every pair straddles two items; F = 2; F = 3"""
+    n_fft, hop, win = 512, 100, 300
+    assert 1 + (T - win) // hop == F
+    xd, rd, g, loss_ref, g_ref = _single(cuda, B, T, n_fft, hop, win, "frames")
+    _five_copies(xd, rd, (n_fft, hop, win), g, loss_ref, g_ref)
+
+
+@pytest.mark.parametrize("n_fft,hop,win", [(256, 8, 64), (2048, 16, 256)])
+def test_persistent_walk_every_item(cuda, n_fft, hop, win):
+    """grid = min(groups, CUs x resident): sized so that every wave of the pair kernel (Stockham at 256, four-step at
+    2048) takes at least three pairs whatever the occupancy query answers, and every item's magnitudes, loss and
+    gradient are compared with the oracle."""
+    B = 4
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    waves, lds, limit = D.pair_walk(n_fft, cus)
+    need = 3 * cus * limit * waves
+    F = -(-2 * need // B)
+    T = win + (F - 1) * hop
+    pairs = (B * F + 1) // 2
+    assert pairs >= need and pairs // (cus * limit * waves) >= 3 and T < 400000
+    print(f"PARITY spectral walk n_fft={n_fft} CUs={cus} waves/workgroup={waves} LDS={lds} resident limit={limit} "
+          f"pairs={pairs} >= 3 x {cus * limit * waves} waves; B={B} T={T} F={F}")
+    _single(cuda, B, T, n_fft, hop, win, "walk")
