@@ -289,6 +289,44 @@ size_t vqa_mse_loss_workspace(int64_t n);
  * that replaces lr (a LearningRateSchedule's value for this step, written by vqa_lr_schedule). */
 int vqa_adam_keras(float* w, const float* g, float* m, float* v, int64_t n, const int64_t* step, float lr,
                    const float* lr_dev, float beta1, float beta2, float eps, float grad_scale, vqa_stream_t stream);
+/* ---- gradient clipping: keras 2.7 OptimizerV2(clipvalue=, clipnorm=, global_clipnorm=), applied on the stream
+ *      to u = grad_scale * g in OptimizerV2._transform_gradients' order (value, norm, global norm).
+ * `modes` is an OR of VQA_CLIP_*; VQA_CLIP_NORM and VQA_CLIP_GLOBAL_NORM exclude each other, and the threshold of
+ * every mode that is set must be finite and > 0 (Keras accepts 0, which zeroes the gradient; refused here). The
+ * thresholds of modes that are not set are ignored.
+ * Variable table (device memory, built once by the caller): variable s is [seg_start[s], seg_start[s + 1]), the
+ * last one ends at n; seg_start[0] = 0, ascending, every entry a multiple of 4 floats (the alignment gap behind a
+ * variable is zero in g and is summed with it). block_seg[b], b in [0, ceil(n / VQA_CLIP_BLOCK)), is the variable
+ * that holds element b * VQA_CLIP_BLOCK. g (and w, m, v) must be 16-byte aligned. */
+enum { VQA_CLIP_VALUE = 1, VQA_CLIP_NORM = 2, VQA_CLIP_GLOBAL_NORM = 4 };
+#define VQA_CLIP_BLOCK 4096 /* floats per workgroup of the two entry points; block_seg is built against it */
+#define VQA_CLIP_STATS 8    /* floats in `stats` */
+/* The norm pass: reads g once.
+ *   u = grad_scale * g;  with VQA_CLIP_VALUE  u = min(max(u, -clipvalue), clipvalue) (a NaN stays a NaN)
+ *   s2[s] = sum of u^2 over variable s;  seg_norm[s] = sqrt(s2[s]) where s2[s] > 0, else s2[s] (0, or a NaN kept)
+ *   stats[0] = sqrt(sum_s sum u^2) before the clamp          stats[1] = sqrt(sum_s s2[s]) (what the norm modes see)
+ *   stats[2] = with VQA_CLIP_GLOBAL_NORM  c * min(1 / stats[1], 1 / c), c = global_clipnorm, NaN when stats[1] is
+ *              not finite (tf.clip_by_global_norm; not exactly 1 below the threshold, as in TF); 1 otherwise
+ *   stats[3] = variables with seg_norm > clipnorm (VQA_CLIP_NORM; else 0)
+ *   stats[4] = elements the clamp changed (VQA_CLIP_VALUE; else 0)              stats[5..7] = 0
+ * Three launches: per block and variable partial sums, per variable sums, the totals. The grid and the order of
+ * every addition depend on (n, the table) only — no float atomics: equal inputs give equal bits, on any rank. */
+int vqa_grad_norm(const float* g, int64_t n, const int64_t* seg_start, const int32_t* block_seg, int nseg,
+                  float grad_scale, int modes, float clipvalue, float clipnorm, float global_clipnorm,
+                  float* seg_norm, float* stats, void* workspace, size_t ws_bytes, vqa_stream_t stream);
+size_t vqa_grad_norm_workspace(int64_t n, int nseg);
+/* vqa_adam_keras on the clipped gradient, g itself left as it is: per element u = grad_scale * g, then
+ *   VQA_CLIP_VALUE        u = min(max(u, -clipvalue), clipvalue)
+ *   VQA_CLIP_NORM         u = (u * clipnorm) / max(seg_norm[s], clipnorm)         (tf.clip_by_norm, s = the
+ *                                                                                  element's variable)
+ *   VQA_CLIP_GLOBAL_NORM  u = u * stats[2]                                        (tf.clip_by_global_norm)
+ * and m, v, w as in vqa_adam_keras with u in place of g * s (same t, alpha, lr_dev and epsilon). seg_norm and
+ * stats are what vqa_grad_norm wrote for the same g, grad_scale, modes and thresholds. */
+int vqa_adam_keras_clipped(float* w, const float* g, float* m, float* v, int64_t n, const int64_t* step, float lr,
+                           const float* lr_dev, float beta1, float beta2, float eps, float grad_scale,
+                           const int64_t* seg_start, const int32_t* block_seg, int nseg, int modes, float clipvalue,
+                           float clipnorm, float global_clipnorm, const float* seg_norm, const float* stats,
+                           vqa_stream_t stream);
 /* keras LearningRateSchedule at the optimizer's device step counter (OptimizerV2._decayed_lr: schedule(float(
  * iterations)), before the step's increment): *lr = f(*step), so a captured train step replays with the right rate.
  * kind 0: p0. kind 1, CustomSchedule (src/transformer/multi_head_attention.py:82-101): p0 = rsqrt(d_model),

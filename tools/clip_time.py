@@ -1,0 +1,58 @@
+"""Time Adam.apply with and without gradient clipping on a real model's parameter store.
+
+    python tools/clip_time.py {cfg2|cfg4} [steps]
+
+cfg2: the benched VQ-VAE's store (968,835 parameters). cfg4: the config-4 prior's (SMALL_PRIOR, ctx 8192). The
+gradient is a fixed normal draw; each variant runs `steps` applies after 3 warm-up ones and prints the mean time
+per apply (device events). Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel times
+(adam_kernel, grad_norm_*_kernel, adam_clip_kernel).
+"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "vae-based-music--deep-generative-models_amd"), ROOT]
+
+import torch  # noqa: E402
+
+from vqa_optim import Adam  # noqa: E402
+
+
+def store_of(which):
+    if which == "cfg2":
+        from vqvae import VQVAE
+        return VQVAE((65536, 1), 3, 64, [3, 2, 2], [2, 2, 2], num_embeddings=2048, residual_width=32,
+                     residual_depth=4, dilation_factor=3, dtype="bf16", device="cuda:0").store
+    from prior import Prior
+    kw = dict(width=128, depth=6, heads=2, blocks=4, attn_stacks=1, drop_out_rate=0.0)
+    ctx = 8192
+    return Prior(2, [(ctx * 16,), (ctx * 4,), (ctx,)], 2048, [3, 2, 2], [2, 2, 2], None, kw, None, dtype="bf16",
+                 device="cuda:0").prior.store
+
+
+def main():
+    which = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
+    steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+    st = store_of(which)
+    g = torch.Generator(device="cuda").manual_seed(5)
+    st.grad[:st.size].copy_(torch.randn(st.size, device="cuda", generator=g) * 1e-2)
+    norm = float(st.grad[:st.size].norm())
+    print(f"{which}: {st.count} parameters, {st.size} floats, {len(st.offsets)} variables, |g| = {norm:.4f}")
+    variants = [("plain", {}), ("global_clipnorm", dict(global_clipnorm=0.5 * norm)),
+                ("clipnorm", dict(clipnorm=0.05)), ("clipvalue+global", dict(clipvalue=0.02, global_clipnorm=0.5 * norm))]
+    for name, clip in variants:
+        opt = Adam(1e-4, **clip)
+        opt.build(st)
+        for _ in range(3):
+            opt.apply(st)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            opt.apply(st)
+        e1.record()
+        torch.cuda.synchronize()
+        print(f"  {name:18s} {e0.elapsed_time(e1) / steps * 1e3:8.1f} us / apply ({steps} applies, eager launches)")
+
+
+if __name__ == "__main__":
+    main()

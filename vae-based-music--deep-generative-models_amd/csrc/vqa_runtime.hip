@@ -4,10 +4,13 @@
 //                    its gradient and the spectral-loss gradient add.
 //   vqa_adam_keras : keras.optimizers.Adam() defaults as applied by TF's ApplyAdam (vqvae.py:144,362):
 //                    one launch over the flat fp32 parameter buffer of all levels.
+//   vqa_grad_norm / vqa_adam_keras_clipped : OptimizerV2's clipvalue / clipnorm / global_clipnorm on the stream
+//                    (a deterministic norm pass, then the same update on the clipped gradient).
 #include "vqa_launch.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -145,6 +148,253 @@ __global__ __launch_bounds__(256) void adam_kernel(float* w, const float* g, flo
   }
 }
 
+// ---- gradient clipping (keras OptimizerV2 clipvalue / clipnorm / global_clipnorm) --------------------------
+// The flat buffers are cut into blocks of VQA_CLIP_BLOCK floats, one workgroup each, in the norm pass and in the
+// clipped update alike. A variable is [seg_start[s], seg_start[s + 1]) (the last one ends at n; the alignment gap
+// behind a variable is zero in the gradient and counts with it); block_seg[b] is the variable that holds the
+// block's first element. Both tables come from the caller; the kernels clamp what they read from them, so a wrong
+// table gives wrong sums, never an access outside the buffers.
+constexpr int kClipBlock = VQA_CLIP_BLOCK;
+static_assert(kClipBlock == 256 * 16, "four float4 per thread and block");
+
+// u = grad_scale * g, then the clipvalue clamp by comparisons (a NaN stays a NaN, as under tf.minimum / tf.maximum)
+__device__ __forceinline__ float clip_clamp(float u, float c) {
+  u = u < -c ? -c : u;
+  return u > c ? c : u;
+}
+
+__device__ __forceinline__ int clip_block_seg(const int* block_seg, int nseg) {
+  const int s = block_seg[blockIdx.x];
+  return s < 0 ? 0 : (s >= nseg ? nseg - 1 : s);
+}
+
+// sum over 256 threads of an unsigned count (integer adds: any order gives the same bits)
+__device__ __forceinline__ unsigned block_count_256(unsigned c, unsigned* slot) {
+  __syncthreads();
+  if (threadIdx.x == 0) *slot = 0u;
+  __syncthreads();
+  if (c) atomicAdd(slot, c);
+  __syncthreads();
+  return *slot;
+}
+
+// Stage 1: block b reads its elements once. Each piece (the part of variable s inside block b) gets the slot b + s of `part`
+// (3 words: sum u^2 before the clamp, after it, clamped elements); b + s grows from one piece to the next, so the
+// slots are distinct, and there are fewer than blocks + nseg of them. Per thread the squares are added in address
+// order, then wave and block trees: the order depends on the layout only.
+__global__ __launch_bounds__(256) void grad_norm_pieces_kernel(const float* g, long long n, const int64_t* seg_start,
+                                                              const int* block_seg, int nseg, float gs, int clamp,
+                                                              float cv, float* part) {
+  __shared__ float red[4];
+  __shared__ unsigned cnt_slot;
+  const long long b0 = (long long)blockIdx.x * kClipBlock;
+  const long long b1 = b0 + kClipBlock < n ? b0 + kClipBlock : n;
+  int s = clip_block_seg(block_seg, nseg);
+  long long p0 = b0;
+  for (;;) {
+    long long p1 = b1;
+    if (s + 1 < nseg) {
+      const long long nx = seg_start[s + 1] & ~3LL;
+      p1 = nx < p0 ? p0 : (nx < b1 ? nx : b1);
+    }
+    float raw = 0.f, cl = 0.f;
+    unsigned cnt = 0u;
+    const long long len4 = (p1 - p0) >> 2;
+    for (long long i = threadIdx.x; i < len4; i += 256) {
+      const f32x4 q = ((const f32x4*)(g + p0))[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float u = q[k] * gs;
+        raw += u * u;
+        if (clamp) {
+          const float c = clip_clamp(u, cv);
+          cnt += (u < -cv || u > cv) ? 1u : 0u;
+          cl += c * c;
+        }
+      }
+    }
+    if (threadIdx.x == 0) {  // the buffer's last one to three elements
+      for (long long i = p0 + 4 * len4; i < p1; ++i) {
+        const float u = g[i] * gs;
+        raw += u * u;
+        if (clamp) {
+          const float c = clip_clamp(u, cv);
+          cnt += (u < -cv || u > cv) ? 1u : 0u;
+          cl += c * c;
+        }
+      }
+    }
+    raw = block_sum_256(raw, red);
+    if (clamp) {
+      cl = block_sum_256(cl, red);
+      cnt = block_count_256(cnt, &cnt_slot);
+    } else {
+      cl = raw;
+    }
+    if (threadIdx.x == 0) {
+      float* o = part + 3 * ((long long)blockIdx.x + s);
+      o[0] = raw;
+      o[1] = cl;
+      ((unsigned*)o)[2] = cnt;
+    }
+    if (p1 >= b1) break;
+    p0 = p1;
+    ++s;
+  }
+}
+
+// Stage 2: one wave per variable adds the variable's pieces, lane l taking pieces l, l + 64, ... in order, then
+// the wave tree. seg_norm = sqrt(s2) where s2 > 0, s2 itself elsewhere (tf.clip_by_norm: 0, or a NaN kept).
+__global__ __launch_bounds__(256) void grad_norm_segments_kernel(const float* part, long long n,
+                                                                const int64_t* seg_start, int nseg, float* seg_raw,
+                                                                float* seg_s2, unsigned* seg_cnt, float* seg_norm) {
+  __shared__ unsigned cnt_slot[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int s = blockIdx.x * 4 + wave;
+  if (lane == 0) cnt_slot[wave] = 0u;
+  __syncthreads();
+  float raw = 0.f, cl = 0.f;
+  unsigned cnt = 0u;
+  if (s < nseg) {
+    long long a = seg_start[s], e = s + 1 < nseg ? seg_start[s + 1] : n;
+    a = a < 0 ? 0 : (a > n ? n : a);
+    e = e < a ? a : (e > n ? n : e);
+    if (e > a) {
+      const long long bl = (e - 1) / kClipBlock;
+      for (long long b = a / kClipBlock + lane; b <= bl; b += 64) {
+        const float* o = part + 3 * (b + s);
+        raw += o[0];
+        cl += o[1];
+        cnt += ((const unsigned*)o)[2];
+      }
+    }
+  }
+  raw = warp_sum(raw);
+  cl = warp_sum(cl);
+  if (cnt) atomicAdd(&cnt_slot[wave], cnt);
+  __syncthreads();
+  if (s < nseg && lane == 0) {
+    seg_raw[s] = raw;
+    seg_s2[s] = cl;
+    seg_cnt[s] = cnt_slot[wave];
+    seg_norm[s] = cl > 0.f ? sqrtf(cl) : cl;
+  }
+}
+
+// Stage 3: one workgroup adds the variables (thread t takes t, t + 256, ... in order, then the block tree) and
+// writes the statistics: [0] |u| before any clipping, [1] |u| after clipvalue (what the norm modes see),
+// [2] the factor global_clipnorm applies (tf.clip_by_global_norm: c * min(1/norm, 1/c), NaN for a non-finite norm;
+// 1 when off), [3] variables whose norm exceeds clipnorm (0 when off), [4] elements clipvalue clamped, [5..7] 0.
+__global__ __launch_bounds__(256) void grad_norm_stats_kernel(const float* seg_raw, const float* seg_s2,
+                                                             const unsigned* seg_cnt, const float* seg_norm, int nseg,
+                                                             int modes, float cn, float gcn, float* stats) {
+  __shared__ float red[4];
+  __shared__ unsigned cnt_slot;
+  float raw = 0.f, cl = 0.f;
+  unsigned cnt = 0u, over = 0u;
+  for (int s = threadIdx.x; s < nseg; s += 256) {
+    raw += seg_raw[s];
+    cl += seg_s2[s];
+    cnt += seg_cnt[s];
+    if ((modes & VQA_CLIP_NORM) && seg_norm[s] > cn) ++over;
+  }
+  raw = block_sum_256(raw, red);
+  cl = block_sum_256(cl, red);
+  cnt = block_count_256(cnt, &cnt_slot);
+  over = block_count_256(over, &cnt_slot);
+  if (threadIdx.x != 0) return;
+  const float norm = sqrtf(cl);
+  float scale = 1.f;
+  if (modes & VQA_CLIP_GLOBAL_NORM) {
+    const float a = 1.f / norm, b = 1.f / gcn;
+    scale = isfinite(norm) ? gcn * (a < b ? a : b) : __builtin_nanf("");
+  }
+  stats[0] = sqrtf(raw);
+  stats[1] = norm;
+  stats[2] = scale;
+  stats[3] = (float)over;
+  stats[4] = (float)cnt;
+  stats[5] = stats[6] = stats[7] = 0.f;
+}
+
+// adam_kernel's update on u = clip(grad_scale * g): clipvalue, then clipnorm ((u * c) / max(norm, c), the NaN of a
+// norm kept), then global_clipnorm (u * stats[2]) — OptimizerV2._transform_gradients' order. g is only read. A
+// float4 never straddles two variables (offsets are multiples of 4), so a thread finds its variable once per
+// float4, walking forward from the block's first one.
+__global__ __launch_bounds__(256) void adam_clip_kernel(float* w, const float* g, float* m, float* v, long long n,
+                                                       const int64_t* step, float lr0, const float* lr_dev, float b1,
+                                                       float b2, float eps, float gs, const int64_t* seg_start,
+                                                       const int* block_seg, int nseg, int modes, float cv, float cn,
+                                                       const float* seg_norm, const float* stats) {
+  const float lr = lr_dev ? lr_dev[0] : lr0;
+  const float t = (float)(step[0] + 1);
+  const float b1p = powf(b1, t), b2p = powf(b2, t);
+  const float alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
+  const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+  const float gscale = (modes & VQA_CLIP_GLOBAL_NORM) ? stats[2] : 1.f;
+  const long long b0 = (long long)blockIdx.x * kClipBlock;
+  int s = 0;
+  long long next = 0x7fffffffffffffffLL;
+  if (modes & VQA_CLIP_NORM) {
+    s = clip_block_seg(block_seg, nseg);
+    if (s + 1 < nseg) next = seg_start[s + 1];
+  }
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const long long p = b0 + 4LL * (it * 256 + (int)threadIdx.x);
+    if (p >= n) break;
+    float den = 1.f;
+    if (modes & VQA_CLIP_NORM) {
+      while (next <= p) {
+        ++s;
+        next = s + 1 < nseg ? seg_start[s + 1] : 0x7fffffffffffffffLL;
+      }
+      const float nm = seg_norm[s];
+      den = nm < cn ? cn : nm;  // max(norm, c); a NaN norm compares false and stays
+    }
+    const int cnt = n - p >= 4 ? 4 : (int)(n - p);
+    f32x4 gq, mq, vq, wq;
+    if (cnt == 4) {
+      gq = *(const f32x4*)(g + p);
+      mq = *(const f32x4*)(m + p);
+      vq = *(const f32x4*)(v + p);
+      wq = *(const f32x4*)(w + p);
+    } else {
+      for (int k = 0; k < 4; ++k) {
+        const bool in = k < cnt;
+        gq[k] = in ? g[p + k] : 0.f;
+        mq[k] = in ? m[p + k] : 0.f;
+        vq[k] = in ? v[p + k] : 0.f;
+        wq[k] = in ? w[p + k] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float u = gq[k] * gs;
+      if (modes & VQA_CLIP_VALUE) u = clip_clamp(u, cv);
+      if (modes & VQA_CLIP_NORM) u = (u * cn) / den;
+      if (modes & VQA_CLIP_GLOBAL_NORM) u = u * gscale;
+      float mi = mq[k], vi = vq[k];
+      mi = mi + (u - mi) * omb1;
+      vi = vi + (u * u - vi) * omb2;
+      mq[k] = mi;
+      vq[k] = vi;
+      wq[k] = wq[k] - (mi * alpha) / (sqrtf(vi) + eps);
+    }
+    if (cnt == 4) {
+      *(f32x4*)(m + p) = mq;
+      *(f32x4*)(v + p) = vq;
+      *(f32x4*)(w + p) = wq;
+    } else {
+      for (int k = 0; k < cnt; ++k) {
+        m[p + k] = mq[k];
+        v[p + k] = vq[k];
+        w[p + k] = wq[k];
+      }
+    }
+  }
+}
+
 // keras LearningRateSchedule evaluated on the device at the optimizer's step counter (OptimizerV2._decayed_lr
 // calls the schedule with float(iterations), the count BEFORE this step's increment), so a captured step replays
 // with the right rate. Host-precomputed float32 constants keep the arithmetic TF's:
@@ -274,6 +524,81 @@ extern "C" int vqa_adam_keras(float* w, const float* g, float* m, float* v, int6
   hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(n, 4096)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
                      (long long)n, step, lr, lr_dev, beta1, beta2, eps, grad_scale);
   VQA_LAUNCHED("adam_kernel");
+  return VQA_OK;
+}
+
+// ---- gradient clipping: argument checks shared by the norm pass and the clipped update
+static long long clip_blocks(int64_t n) { return (n + kClipBlock - 1) / kClipBlock; }
+
+static bool clip_threshold_ok(int modes, int bit, float c) { return !(modes & bit) || (std::isfinite(c) && c > 0.f); }
+
+static int clip_check(const char* what, int64_t n, const void* seg_start, const void* block_seg, int nseg, int modes,
+                      float clipvalue, float clipnorm, float global_clipnorm) {
+  VQA_ARG(n > 0, "%s: n must be > 0 (got %lld)", what, (long long)n);
+  VQA_ARG(nseg > 0, "%s: nseg must be > 0 (got %d)", what, nseg);
+  VQA_ARG(clip_blocks(n) + nseg < (1LL << 31), "%s: n %lld too large", what, (long long)n);
+  VQA_ARG(seg_start && block_seg, "%s: null variable table", what);
+  VQA_ARG((modes & ~(VQA_CLIP_VALUE | VQA_CLIP_NORM | VQA_CLIP_GLOBAL_NORM)) == 0, "%s: unknown mode bits %d", what,
+          modes);
+  VQA_ARG(!((modes & VQA_CLIP_NORM) && (modes & VQA_CLIP_GLOBAL_NORM)),
+          "%s: clipnorm and global_clipnorm exclude each other", what);
+  VQA_ARG(clip_threshold_ok(modes, VQA_CLIP_VALUE, clipvalue), "%s: clipvalue must be finite and > 0 (got %g)", what,
+          (double)clipvalue);
+  VQA_ARG(clip_threshold_ok(modes, VQA_CLIP_NORM, clipnorm), "%s: clipnorm must be finite and > 0 (got %g)", what,
+          (double)clipnorm);
+  VQA_ARG(clip_threshold_ok(modes, VQA_CLIP_GLOBAL_NORM, global_clipnorm),
+          "%s: global_clipnorm must be finite and > 0 (got %g)", what, (double)global_clipnorm);
+  return VQA_OK;
+}
+
+// 3 words per piece slot (blocks + nseg slots), then per variable: sum u^2 before the clamp, after it, clamped count
+extern "C" size_t vqa_grad_norm_workspace(int64_t n, int nseg) {
+  if (n < 1 || nseg < 1) return 0;
+  return (size_t)(3 * (clip_blocks(n) + nseg) + 3 * (long long)nseg) * sizeof(float);
+}
+
+extern "C" int vqa_grad_norm(const float* g, int64_t n, const int64_t* seg_start, const int32_t* block_seg, int nseg,
+                             float grad_scale, int modes, float clipvalue, float clipnorm, float global_clipnorm,
+                             float* seg_norm, float* stats, void* workspace, size_t ws_bytes, vqa_stream_t stream) {
+  const int rc = clip_check("grad_norm", n, seg_start, block_seg, nseg, modes, clipvalue, clipnorm, global_clipnorm);
+  if (rc != VQA_OK) return rc;
+  VQA_ARG(g && seg_norm && stats, "grad_norm: null pointer");
+  VQA_ARG((uintptr_t)g % 16 == 0, "grad_norm: the gradient must be 16-byte aligned");
+  VQA_ARG(workspace && ws_bytes >= vqa_grad_norm_workspace(n, nseg), "grad_norm: workspace too small (%zu B, need %zu)",
+          ws_bytes, vqa_grad_norm_workspace(n, nseg));
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = (int)clip_blocks(n);
+  float* part = (float*)workspace;
+  float* seg_raw = part + 3 * ((long long)nb + nseg);
+  float* seg_s2 = seg_raw + nseg;
+  unsigned* seg_cnt = (unsigned*)(seg_s2 + nseg);
+  hipLaunchKernelGGL(grad_norm_pieces_kernel, dim3(nb), dim3(256), 0, s, g, (long long)n, seg_start, block_seg, nseg,
+                     grad_scale, (modes & VQA_CLIP_VALUE) ? 1 : 0, clipvalue, part);
+  VQA_LAUNCHED("grad_norm_pieces_kernel");
+  hipLaunchKernelGGL(grad_norm_segments_kernel, dim3((nseg + 3) / 4), dim3(256), 0, s, (const float*)part, (long long)n,
+                     seg_start, nseg, seg_raw, seg_s2, seg_cnt, seg_norm);
+  VQA_LAUNCHED("grad_norm_segments_kernel");
+  hipLaunchKernelGGL(grad_norm_stats_kernel, dim3(1), dim3(256), 0, s, (const float*)seg_raw, (const float*)seg_s2,
+                     (const unsigned*)seg_cnt, (const float*)seg_norm, nseg, modes, clipnorm, global_clipnorm, stats);
+  VQA_LAUNCHED("grad_norm_stats_kernel");
+  return VQA_OK;
+}
+
+extern "C" int vqa_adam_keras_clipped(float* w, const float* g, float* m, float* v, int64_t n, const int64_t* step,
+                                      float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                                      float grad_scale, const int64_t* seg_start, const int32_t* block_seg, int nseg,
+                                      int modes, float clipvalue, float clipnorm, float global_clipnorm,
+                                      const float* seg_norm, const float* stats, vqa_stream_t stream) {
+  const int rc =
+      clip_check("adam_clipped", n, seg_start, block_seg, nseg, modes, clipvalue, clipnorm, global_clipnorm);
+  if (rc != VQA_OK) return rc;
+  VQA_ARG(w && g && m && v && step && seg_norm && stats, "adam_clipped: null pointer");
+  VQA_ARG(((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0,
+          "adam_clipped: w, g, m and v must be 16-byte aligned");
+  hipLaunchKernelGGL(adam_clip_kernel, dim3((int)clip_blocks(n)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
+                     (long long)n, step, lr, lr_dev, beta1, beta2, eps, grad_scale, seg_start, block_seg, nseg, modes,
+                     clipvalue, clipnorm, seg_norm, stats);
+  VQA_LAUNCHED("adam_clip_kernel");
   return VQA_OK;
 }
 

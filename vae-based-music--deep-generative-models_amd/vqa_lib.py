@@ -48,6 +48,7 @@ EXPORTED = [
     "vqa_corpus_steps_per_epoch", "vqa_corpus_batch", "vqa_pcm_encode", "vqa_code_batch",
     "vqa_resample", "vqa_resample_route",
     "vqa_attn_weights_elems", "vqa_attn_weights",
+    "vqa_grad_norm", "vqa_grad_norm_workspace", "vqa_adam_keras_clipped",
 ]
 
 
@@ -92,6 +93,10 @@ _SIGS = {
     "vqa_mse_loss": (_I, [_P, _P, _P, _P, _P, _L, _P, _S, _P]),
     "vqa_mse_loss_workspace": (_S, [_L]),
     "vqa_adam_keras": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _F, _F, _F, _F, _P]),
+    "vqa_grad_norm": (_I, [_P, _L, _P, _P, _I, _F, _I, _F, _F, _F, _P, _P, _P, _S, _P]),
+    "vqa_grad_norm_workspace": (_S, [_L, _I]),
+    "vqa_adam_keras_clipped": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _F, _F, _F, _F, _P, _P, _I, _I, _F, _F, _F, _P,
+                                    _P, _P]),
     "vqa_lr_schedule": (_I, [_P, _P, _I, _F, _F, _F, _F, _P]),
     "vqa_counter_add": (_I, [_P, _L, _P]),
     "vqa_step_metrics": (_I, [_P, _P, _P, _I, _F, _P]),
@@ -512,6 +517,32 @@ def mse_loss(x, r, extra, dr, loss_out):
 def adam_keras(w, g, m, v, step, lr, beta1, beta2, eps, grad_scale, lr_dev=None):
     _check(lib().vqa_adam_keras(ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), ptr(step), float(lr), ptr(lr_dev), beta1,
                                 beta2, eps, grad_scale, stream()), "vqa_adam_keras")
+
+
+# gradient clipping (include/vqa.h): mode bits, floats per workgroup of the variable table, floats in `stats`
+CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = 1, 2, 4
+CLIP_BLOCK = 4096
+CLIP_STATS = 8
+
+
+def grad_norm_workspace(n: int, nseg: int) -> int:
+    return lib().vqa_grad_norm_workspace(n, nseg)
+
+
+def grad_norm(g, seg_start, block_seg, grad_scale, modes, clipvalue, clipnorm, global_clipnorm, seg_norm, stats,
+              ws):
+    """The norm pass of a clipped step (vqa_grad_norm): per-variable norms and the statistics of grad_scale * g."""
+    _check(lib().vqa_grad_norm(ptr(g), g.numel(), ptr(seg_start), ptr(block_seg), seg_start.numel(), grad_scale,
+                               int(modes), clipvalue, clipnorm, global_clipnorm, ptr(seg_norm), ptr(stats), ptr(ws),
+                               ws.numel(), stream()), "vqa_grad_norm")
+
+
+def adam_keras_clipped(w, g, m, v, step, lr, beta1, beta2, eps, grad_scale, seg_start, block_seg, modes, clipvalue,
+                       clipnorm, global_clipnorm, seg_norm, stats, lr_dev=None):
+    _check(lib().vqa_adam_keras_clipped(ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), ptr(step), float(lr), ptr(lr_dev),
+                                        beta1, beta2, eps, grad_scale, ptr(seg_start), ptr(block_seg),
+                                        seg_start.numel(), int(modes), clipvalue, clipnorm, global_clipnorm,
+                                        ptr(seg_norm), ptr(stats), stream()), "vqa_adam_keras_clipped")
 
 
 def lr_schedule(step, lr_out, kind, p):

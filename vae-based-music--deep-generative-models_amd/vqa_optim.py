@@ -6,28 +6,80 @@ train step replays with the right t. `learning_rate` is a float or a keras Learn
 (schedules.CustomSchedule — src/transformer/multi_head_attention.py:82-101 — or ExponentialDecay): a schedule
 is evaluated on the device from `iterations` (vqa_lr_schedule) right before the update, so graph replay stays
 valid.
+
+Gradient clipping is OptimizerV2's: `clipvalue`, `clipnorm` (per variable) and `global_clipnorm`, applied in
+that order to the aggregated gradient grad_scale * g (after the data-parallel exchange, as Keras clips after
+aggregation). The norms, the scale and the clipped update are kernels on the step's stream (vqa_grad_norm,
+vqa_adam_keras_clipped), so a captured step replays them; nothing is read back. The gradient buffer is not
+rewritten. Deviation from Keras: a threshold of 0 (which Keras accepts and which zeroes every gradient) is
+refused, as is any value that is not finite and > 0. The thresholds are configuration, not state: checkpoints
+hold nothing of them.
 """
 from __future__ import annotations
 
+import math
+
+import numpy as np
 import torch
 
 import vqa_lib as V
 from schedules import LearningRateSchedule
 
+# Adam.grad_stats() keys, in the order of vqa_grad_norm's `stats`
+GRAD_STATS = ("global_norm", "clipped_global_norm", "global_scale", "clipnorm_variables", "clipvalue_elements")
+
+
+def _threshold(name, value):
+    if value is None:
+        return None
+    try:
+        c = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: a finite number > 0 or None (got {value!r})") from None
+    if not (math.isfinite(c) and c > 0.0):
+        raise ValueError(f"{name}: a finite number > 0 or None (got {value!r}; Keras' 0 is refused)")
+    return c
+
+
+def clip_tables(offsets, size: int):
+    """The variable table of vqa_grad_norm / vqa_adam_keras_clipped for a ParamStore layout (host, numpy):
+    seg_start (int64, one ascending offset per variable) and block_seg (int32, per block of V.CLIP_BLOCK floats the
+    variable that holds the block's first element)."""
+    seg = np.array(sorted(int(o) for o, _ in offsets.values()), np.int64)
+    if seg.size == 0 or seg[0] != 0 or np.any(seg % 4) or np.any(np.diff(seg) <= 0) or seg[-1] >= size:
+        raise ValueError("clip_tables: offsets must start at 0, ascend and be multiples of 4 floats")
+    nblk = -(-size // V.CLIP_BLOCK)
+    first = np.arange(nblk, dtype=np.int64) * V.CLIP_BLOCK
+    block_seg = (np.searchsorted(seg, first, side="right") - 1).astype(np.int32)
+    return seg, block_seg
+
 
 class Adam:
-    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **kwargs):
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, *, clipvalue=None,
+                 clipnorm=None, global_clipnorm=None, **kwargs):
         if callable(learning_rate) and not isinstance(learning_rate, LearningRateSchedule):
             # a host callable cannot be evaluated inside a replayed hipGraph
             raise TypeError("learning_rate: a float or a schedules.LearningRateSchedule (device-evaluated)")
+        if clipnorm is not None and global_clipnorm is not None:
+            raise ValueError(f"Cannot accept both `clipnorm` and `global_clipnorm`, received: clipnorm={clipnorm}, "
+                             f"global_clipnorm={global_clipnorm}")
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = learning_rate, beta_1, beta_2, epsilon
+        self.clipvalue = _threshold("clipvalue", clipvalue)
+        self.clipnorm = _threshold("clipnorm", clipnorm)
+        self.global_clipnorm = _threshold("global_clipnorm", global_clipnorm)
         self.iterations = None
         self.m = self.v = None
         self._lr_dev = None
+        self._clip = None  # device tables, norms, statistics and workspace of the clipped path (build)
 
     @property
     def scheduled(self) -> bool:
         return isinstance(self.learning_rate, LearningRateSchedule)
+
+    @property
+    def clip_modes(self) -> int:
+        return ((V.CLIP_VALUE if self.clipvalue is not None else 0) | (V.CLIP_NORM if self.clipnorm is not None else 0)
+                | (V.CLIP_GLOBAL_NORM if self.global_clipnorm is not None else 0))
 
     def build(self, store):
         dev = store.flat.device
@@ -35,12 +87,35 @@ class Adam:
         self.v = torch.zeros_like(store.flat)
         self.iterations = torch.zeros(1, dtype=torch.int64, device=dev)
         self._lr_dev = torch.zeros(1, dtype=torch.float32, device=dev) if self.scheduled else None
+        if self.clip_modes:
+            # allocated once: a captured step keeps these pointers
+            seg, block_seg = clip_tables(store.offsets, store.size)
+            self._clip = dict(
+                seg_start=torch.from_numpy(seg).to(dev), block_seg=torch.from_numpy(block_seg).to(dev),
+                seg_norm=torch.zeros(seg.size, dtype=torch.float32, device=dev),
+                stats=torch.zeros(V.CLIP_STATS, dtype=torch.float32, device=dev),
+                ws=V.workspace(V.grad_norm_workspace(store.size, seg.size), dev))
 
     def current_learning_rate(self) -> float:
         """The rate the next apply() uses (host evaluation of the schedule at the device step count)."""
         if not self.scheduled:
             return float(self.learning_rate)
         return self.learning_rate(int(self.iterations.item()))
+
+    def grad_stats(self):
+        """The last clipped step's statistics as 0-dim device tensors (views of one buffer the step writes; no
+        host sync): the global norm of grad_scale * g before any clipping, the global norm after `clipvalue` (what
+        the norm modes see), the factor `global_clipnorm` applied (1 when off), the number of variables whose norm
+        exceeded `clipnorm`, the number of elements `clipvalue` clamped."""
+        if self._clip is None:
+            raise RuntimeError("grad_stats: no clipping configured, or the optimizer is not built yet")
+        return {k: self._clip["stats"][i] for i, k in enumerate(GRAD_STATS)}
+
+    def variable_grad_norms(self) -> torch.Tensor:
+        """Per-variable norms of the last clipped step's gradient (after `clipvalue`), in offset order."""
+        if self._clip is None:
+            raise RuntimeError("variable_grad_norms: no clipping configured, or the optimizer is not built yet")
+        return self._clip["seg_norm"]
 
     def apply(self, store, grad_scale: float = 1.0):
         if self.m is None:
@@ -51,6 +126,16 @@ class Adam:
             V.lr_schedule(self.iterations, self._lr_dev, kind, p)
         else:
             lr = self.learning_rate
-        V.adam_keras(store.flat, store.grad[:store.size], self.m, self.v, self.iterations, lr,
-                     self.beta_1, self.beta_2, self.epsilon, grad_scale, lr_dev=self._lr_dev)
+        g = store.grad[:store.size]
+        if not self.clip_modes:
+            V.adam_keras(store.flat, g, self.m, self.v, self.iterations, lr,
+                         self.beta_1, self.beta_2, self.epsilon, grad_scale, lr_dev=self._lr_dev)
+        else:
+            c = self._clip
+            thr = (self.clipvalue or 0.0, self.clipnorm or 0.0, self.global_clipnorm or 0.0)
+            V.grad_norm(g, c["seg_start"], c["block_seg"], grad_scale, self.clip_modes, *thr, c["seg_norm"],
+                        c["stats"], c["ws"])
+            V.adam_keras_clipped(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2,
+                                 self.epsilon, grad_scale, c["seg_start"], c["block_seg"], self.clip_modes, *thr,
+                                 c["seg_norm"], c["stats"], lr_dev=self._lr_dev)
         V.counter_add(self.iterations, 1)
