@@ -682,6 +682,32 @@ int vqa_prior_decode_primed(const vqa_prior_layer* layers, int depth, const floa
                             int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx, int width,
                             int heads, int blocks, int bins, int out_ld, int64_t start, uint64_t seed,
                             const int64_t* prime, int prime_len, float temperature, int top_k, vqa_stream_t stream);
+/* vqa_prior_decode_primed with nucleus (top-p) sampling and the size of every draw's candidate set
+ * (vqa_prior_decode_primed forwards here with 1.0f, NULL and launches what it launched before).
+ * For one row of logits lg[0 .. bins), temperature T, top_k and top_p = p:
+ *   1. S = the bins that survive top-k (logit >= the k-th largest, ties included; every bin with top-k off);
+ *   2. w[v] = exp((lg[v] - max lg) / T) for v in S;
+ *   3. Z = sum of w over S, A(t) = sum of w[v] over the v in S with lg[v] > t (the mass strictly above a logit);
+ *   4. bin v takes part in the draw iff v in S and A(lg[v]) < p Z: the smallest set of top bins whose mass reaches
+ *      p. Bins with equal logits stay in or go out together; the top bin always stays;
+ *   5. the draw is unchanged among them: argmax of lg / T + G, noise keyed by (seed, sample, absolute step, bin),
+ *      ties of the score to the lowest index.
+ * top_p must be finite with 0 < top_p <= 1; 1 is off and is decided on the host (the filter is not run, so weights
+ * that underflow drop no bin). The threshold is found on the device by a radix select on mass: w in fp32, summed
+ * as 64-bit fixed point with 36 fractional bits through integer LDS atomics (every sum exact, so the result is
+ * bitwise the same run to run), four fixed rounds whatever the data.
+ * kept (N, steps) int32 or NULL: for every step whose head runs, the number of bins that took part in the draw
+ * (after top-k and top-p); 0 for the primed steps whose head is skipped. Computed only when given; it may be asked
+ * for with top_p = 1.
+ * VQA_E_INVALID_ARG before any launch: what vqa_prior_decode_primed rejects, and a top_p that is not finite or
+ * outside (0, 1]. */
+int vqa_prior_decode_filtered(const vqa_prior_layer* layers, int depth, const float* x_embedding,
+                              const float* pos_embedding, const float* out_kernel, const float* out_bias,
+                              const float* ycond, const float* xcond, const int64_t* forced, float* logits,
+                              int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx, int width,
+                              int heads, int blocks, int bins, int out_ld, int64_t start, uint64_t seed,
+                              const int64_t* prime, int prime_len, float temperature, int top_k, float top_p,
+                              int32_t* kept, vqa_stream_t stream);
 
 #ifdef __cplusplus
 }

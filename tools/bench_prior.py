@@ -9,8 +9,8 @@ Synthetic codes (uniform over the codebook), random-init weights. The cpu leg ti
 (oracle/prior_ref.py, torch CPU fp32) on a bounded sample.
     python tools/bench_prior.py [--batch 8] [--steps 10] [--samples 16] [--sample-len 2048] [--no-cpu]
 The sample leg takes the primed decode's options: --prime-len P (the first P positions are given, random codes;
-P = --sample-len times the primed positions alone, head skipped), --temperature, --top-k, and --repeats R (R timed
-launches in one process; ms_per_position is their median, ms_per_position_repeats lists them).
+P = --sample-len times the primed positions alone, head skipped), --temperature, --top-k, --top-p, and --repeats R
+(R timed launches in one process; ms_per_position is their median, ms_per_position_repeats lists them).
   feed  : (--only feed; never part of the default run) the config-4 train step fed three ways, in one process:
           (a) captured, codes copied in (the `train` leg's step), (b) captured on a code_feed.CodeFeed over a
           device-resident corpus of random codes (--tracks tracks of 4 ctx codes, windows hopping by ctx / 2),
@@ -165,6 +165,7 @@ def main():
     ap.add_argument("--prime-len", type=int, default=0)
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--no-cpu", action="store_true")
@@ -276,9 +277,9 @@ def main():
         up = torch.randint(0, a.bins - 1, (a.samples, a.ctx // 4), device=dev, generator=g)
         prime = (torch.randint(0, a.bins - 1, (a.samples, a.prime_len), device=dev, generator=g)
                  if a.prime_len else None)
-        opts = dict(prime=prime, temperature=a.temperature, top_k=a.top_k)
+        opts = dict(prime=prime, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
         m.sample(a.samples, max_length=16, x_cond=up, seed=1, temperature=a.temperature,
-                 top_k=a.top_k)  # warm-up (conditioner + the decode kernel that is timed)
+                 top_k=a.top_k, top_p=a.top_p)  # warm-up (conditioner + the decode kernel that is timed)
         torch.cuda.synchronize()
         els = []
         for _ in range(max(1, a.repeats)):  # one window per launch; an error raises and ends the run
@@ -291,7 +292,7 @@ def main():
                           "value": round(a.samples * a.sample_len / el, 1), "unit": "tokens/s", "n_gpus": 1,
                           "ms_per_position": round(el / a.sample_len * 1e3, 4),
                           "ms_per_position_repeats": [round(e / a.sample_len * 1e3, 4) for e in els],
-                          "prime_len": a.prime_len, "temperature": a.temperature, "top_k": a.top_k,
+                          "prime_len": a.prime_len, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
                           "samples": a.samples,
                           "positions": a.sample_len, "dtype": "fp32 (decode)",
                           "config": {"workload": "BASELINE config 5", "ctx": a.ctx, "bins": a.bins, **kw},

@@ -1658,7 +1658,9 @@ __global__ __launch_bounds__(256) void rowsum_final_kernel(const float* part, in
 // reproduces the rest bit for bit. kPrimed = true is the instantiation that knows the prime; without one the
 // step loop is the unprimed decode's. kFilter = true is the instantiation with a temperature and / or top-k
 // (score = logit / temperature + G over the bins whose logit is >= the k-th largest of the row); the default
-// (temperature 1, top-k off) runs kFilter = false, whose arithmetic is the unfiltered decode's.
+// (temperature 1, top-k off) runs kFilter = false, whose arithmetic is the unfiltered decode's. kFilter = 2
+// (vqa_prior_decode_filtered with top_p < 1 or a `kept` output) is kFilter = 1 plus the nucleus threshold
+// (dec_nucleus_threshold) and the count of the bins that took part in the draw.
 constexpr int kDecMaxLayers = 8;
 constexpr int kDecW = 128;   // model width
 constexpr int kDecAW = 32;   // attention width (m_attn 0.25)
@@ -1698,6 +1700,8 @@ struct DecArgs {
   int prime_len;          // 0 <= prime_len <= steps (0 without a prime)
   int topk;               // 0: off, else 1 <= topk < bins (kFilter only)
   float temp;             // temperature, finite and > 0 (kFilter only)
+  float topp;             // nucleus mass, 0 < topp <= 1, >= 1: off (kFilter = 2 only)
+  int* kept;              // (N, steps) bins that took part in each draw, or null (kFilter = 2 only)
 };
 
 // y[o] = b[o] + sum_k x[k] W[k][o] (W row-major (K, O), O % 4 == 0): thread (4-output chunk c, k-group kg) sums
@@ -1835,7 +1839,93 @@ __device__ float dec_kth_largest(const float* v, int n, int k, int* hist, int* s
   return dec_unkey(prefix);
 }
 
-template <bool kPrimed, bool kFilter>
+// The nucleus (top-p) threshold of the row v[0 .. n) (n <= 2048, v in LDS), by all 256 threads: the logit t* with
+// M(> t*) < p Z <= M(>= t*), where M is the mass of the bins of S = {v >= thr} (thr: the top-k threshold, -inf
+// without one) beyond a logit value and Z = M(>= -inf). The bins with v >= t* are then exactly the bins of S with
+// (mass strictly above their logit) < p Z: the smallest set of top bins whose mass reaches p, ties in or out
+// together, the top bin always in.
+// Arithmetic: m = max of the row (fmaxf, so NaNs are skipped); a bin of S weighs w = expf((v - m) / temp) in fp32
+// (0 <= w <= 1; NaN -> 0), and its mass is the integer q = trunc(w * 2^36): exact for an fp32 w, 0 below 2^-36.
+// Masses are summed as 64-bit integers (at most 2048 * 2^36 = 2^47), so every sum is exact and independent of the
+// order of the LDS atomics. The target is the integer ceil(p * Zq), formed in fp64 (p and Zq < 2^53 are exact
+// there): for an integer mass, M < p Zq <=> M < ceil(p Zq); 1 <= target <= Zq as 0 < p <= 1 <= Zq.
+// t* comes from dec_kth_largest's radix select over the keys, most significant byte first, selecting on mass
+// instead of count: four rounds whatever the data; a round adds, in hist[256], the mass of every key that matches
+// the bytes chosen so far to the bucket of its next byte; wave 0 scans the buckets from the top for the byte d with
+// (mass of the larger bytes) < target <= (mass of the bytes >= d), which becomes the next chosen byte, and the
+// target drops by the mass above it. 1 <= target <= (matching mass) holds from round to round, so one d always
+// qualifies and t* is the key of a bin with a nonzero mass. A row without any mass (m = +-inf or all NaN) leaves
+// the target 0: no byte qualifies, the rounds still run, and thr is returned as it came.
+// hist holds 256 and sel 2 64-bit words, stat 4 floats; all three are free again after the caller's next barrier.
+constexpr float kDecMassScale = 68719476736.f;  // 2^36
+__device__ float dec_nucleus_threshold(const float* v, int n, float thr, float temp, float p,
+                                       unsigned long long* hist, unsigned long long* sel, float* stat) {
+  typedef unsigned long long u64;
+  const int tid = threadIdx.x;
+  float m = -INFINITY;
+  for (int e = tid; e < n; e += 256) m = fmaxf(m, v[e]);
+  m = wave_max_f(m);
+  if ((tid & 63) == 0) stat[tid >> 6] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(stat[0], stat[1]), fmaxf(stat[2], stat[3]));
+  // thread tid owns the bins tid + 256 j: their keys and masses stay in registers over the four rounds
+  unsigned key[8];
+  u64 q[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int e = tid + 256 * j;
+    key[j] = 0;
+    q[j] = 0;
+    if (e < n) {
+      const float lg = v[e];
+      key[j] = dec_key(lg);
+      if (lg >= thr) {
+        float w = expf((lg - m) / temp);
+        w = w >= 0.f ? fminf(w, 1.0f) : 0.f;  // NaN: no mass
+        q[j] = (u64)(w * kDecMassScale);
+      }
+    }
+  }
+  unsigned prefix = 0, mask = 0;
+  u64 tgt = 0;
+#pragma unroll 1
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    hist[tid] = 0;
+    __syncthreads();
+    if (tid == 0) { sel[0] = 0; sel[1] = 0; }
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (q[j] != 0 && (key[j] & mask) == prefix) atomicAdd(&hist[(key[j] >> shift) & 255u], q[j]);
+    __syncthreads();
+    if (tid < 64) {
+      // lane L holds the bytes 255 - 4L .. 252 - 4L, largest first; `above` = mass of the keys with a larger byte.
+      // The 64-bit scan is two int scans of the low 24 and the high bits (t < 2^47: neither can overflow).
+      u64 c[4], t = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { c[j] = hist[255 - 4 * tid - j]; t += c[j]; }
+      const int lo = xl::incl_scan((int)(t & 0xFFFFFFu)), hi = xl::incl_scan((int)(t >> 24));
+      if (shift == 24) {  // first round: every key matches, lane 63 holds Zq
+        const u64 zq = ((u64)(unsigned)__builtin_amdgcn_readlane(hi, 63) << 24) +
+                       (u64)(unsigned)__builtin_amdgcn_readlane(lo, 63);
+        tgt = (u64)ceil((double)p * (double)zq);
+      }
+      u64 above = ((u64)(unsigned)hi << 24) + (u64)(unsigned)lo - t;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (above < tgt && tgt <= above + c[j]) { sel[0] = (u64)(255 - 4 * tid - j); sel[1] = tgt - above; }
+        above += c[j];
+      }
+    }
+    __syncthreads();
+    prefix |= (unsigned)sel[0] << shift;
+    mask |= 255u << shift;
+    tgt = sel[1];
+  }
+  if (tgt == 0) return thr;
+  return fmaxf(thr, dec_unkey(prefix));
+}
+
+template <bool kPrimed, int kFilter>
 __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
   __shared__ __attribute__((aligned(16))) float x[kDecW], x1[kDecW], hb[kDecW], r1[kDecW];
   __shared__ float ring[kDecMaxLayers][3][kDecW];
@@ -1966,40 +2056,56 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
       if (primed && !a.logits) {
         tok = a.prime[(size_t)n * a.prime_len + i];
         if (tid == 0) a.tokens[(size_t)n * (a.steps + 1) + i + 1] = tok;
+        if constexpr (kFilter == 2) {
+          if (a.kept && tid == 0) a.kept[(size_t)n * a.steps + i] = 0;
+        }
         continue;
       }
     }
     // output head + Gumbel-max
     dec_matvec(x, kDecW, a.hw, a.hb, scr, a.ldo, bestv);  // scr holds the logits (ldo >= bins columns)
     float thr = -INFINITY;  // top-k: only the bins with logit >= the k-th largest of the row take part
-    if constexpr (kFilter) {
+    if constexpr (kFilter != 0) {
       if (a.topk > 0) thr = dec_kth_largest(scr, a.bins, a.topk, besti, ksel);
     }
+    if constexpr (kFilter == 2) {
+      // bestv (the head mat-vec's scratch) is free: 256 + 2 64-bit words of it hold the mass histogram
+      if (a.topp < 1.0f)
+        thr = dec_nucleus_threshold(scr, a.bins, thr, a.temp, a.topp, (unsigned long long*)bestv,
+                                    (unsigned long long*)bestv + 256, stat);
+    }
     float bv = -INFINITY;
-    int bi = 0;
+    int bi = 0, nk = 0;  // nk: this thread's bins that take part (kFilter = 2)
     for (int v = tid; v < a.bins; v += 256) {
       const float lg = scr[v];
       if (a.logits) a.logits[((size_t)n * a.steps + i) * a.bins + v] = lg;
-      if constexpr (kFilter) {
+      if constexpr (kFilter != 0) {
         if (!(lg >= thr)) continue;
       }
+      if constexpr (kFilter == 2) ++nk;
       const float u = prior_uniform(a.seed, (uint64_t)n, (uint64_t)i, (uint64_t)v);
       float z;
-      if constexpr (kFilter) z = lg / a.temp + (-logf(-logf(u)));
+      if constexpr (kFilter != 0) z = lg / a.temp + (-logf(-logf(u)));
       else z = lg + (-logf(-logf(u)));
       if (z > bv) { bv = z; bi = v; }
     }
     __syncthreads();
     bestv[tid] = bv;
     besti[tid] = bi;
+    int* nkept = (int*)scr;  // the logits are dead past the barrier above (kFilter = 2: the counts ride the tree)
+    if constexpr (kFilter == 2) nkept[tid] = nk;
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
       if (tid < w) {
         const float ov = bestv[tid + w];
         const int oi = besti[tid + w];
         if (ov > bestv[tid] || (ov == bestv[tid] && oi < besti[tid])) { bestv[tid] = ov; besti[tid] = oi; }
+        if constexpr (kFilter == 2) nkept[tid] += nkept[tid + w];
       }
       __syncthreads();
+    }
+    if constexpr (kFilter == 2) {
+      if (a.kept && tid == 0) a.kept[(size_t)n * a.steps + i] = nkept[0];
     }
     int64_t samp = besti[0];
     if constexpr (kPrimed) {
@@ -2599,13 +2705,13 @@ extern "C" size_t vqa_prior_decode_cache_bytes(int N, int depth, int ctx) {
   return ((size_t)2 * N * depth * ctx * kDecAW + (size_t)depth * kDecComposed) * sizeof(float);
 }
 
-extern "C" int vqa_prior_decode_primed(const vqa_prior_layer* layers, int depth, const float* x_embedding,
-                                       const float* pos_embedding, const float* out_kernel, const float* out_bias,
-                                       const float* ycond, const float* xcond, const int64_t* forced, float* logits,
-                                       int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx,
-                                       int width, int heads, int blocks, int bins, int out_ld, int64_t start,
-                                       uint64_t seed, const int64_t* prime, int prime_len, float temperature,
-                                       int top_k, vqa_stream_t stream) {
+extern "C" int vqa_prior_decode_filtered(const vqa_prior_layer* layers, int depth, const float* x_embedding,
+                                         const float* pos_embedding, const float* out_kernel, const float* out_bias,
+                                         const float* ycond, const float* xcond, const int64_t* forced, float* logits,
+                                         int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx,
+                                         int width, int heads, int blocks, int bins, int out_ld, int64_t start,
+                                         uint64_t seed, const int64_t* prime, int prime_len, float temperature,
+                                         int top_k, float top_p, int32_t* kept, vqa_stream_t stream) {
   VQA_ARG(layers && x_embedding && pos_embedding && out_kernel && out_bias && tokens && cache && N > 0 && steps > 0 &&
               steps <= ctx && blocks > 0 && ctx % blocks == 0 && bins > 0 && out_ld >= bins && out_ld % 4 == 0 &&
               out_ld <= 2048,
@@ -2617,6 +2723,8 @@ extern "C" int vqa_prior_decode_primed(const vqa_prior_layer* layers, int depth,
   VQA_ARG(std::isfinite(temperature) && temperature > 0.f, "prior_decode: temperature %g is not finite and > 0",
           (double)temperature);
   VQA_ARG(top_k >= 0 && top_k <= bins, "prior_decode: top_k %d outside [0, bins %d]", top_k, bins);
+  VQA_ARG(std::isfinite(top_p) && top_p > 0.f && top_p <= 1.0f, "prior_decode: top_p %g is not finite and in (0, 1]",
+          (double)top_p);
   VQA_REQUIRE(depth > 0 && depth <= kDecMaxLayers && width == kDecW && heads > 0 && kDecAW % heads == 0 &&
                   kDecAW / heads <= 32 && ctx / blocks <= kDecMaxL && heads <= 4,
               VQA_E_UNSUPPORTED, "prior_decode: depth %d width %d heads %d block %d unsupported", depth, width, heads,
@@ -2653,15 +2761,34 @@ extern "C" int vqa_prior_decode_primed(const vqa_prior_layer* layers, int depth,
   a.prime_len = prime_len;
   a.topk = (top_k > 0 && top_k < bins) ? top_k : 0;  // 0 and bins: every bin takes part
   a.temp = temperature;
-  const bool filter = a.topk > 0 || temperature != 1.0f;
+  a.topp = top_p;
+  a.kept = kept;
+  // 0: the unfiltered decode; 1: a temperature and / or top-k; 2: top-p on (top_p = 1 is off, decided here: the
+  // filter is not run, so weights that underflow drop no bin) or the kept counts asked for
+  const int filter = (top_p < 1.0f || kept) ? 2 : (a.topk > 0 || temperature != 1.0f) ? 1 : 0;
   hipLaunchKernelGGL(prior_decode_prep_kernel, dim3(64, depth), dim3(256), 0, (hipStream_t)stream, a);
   VQA_LAUNCHED("prior_decode_prep_kernel");
   const bool primed = prime_len > 0;
-  void (*kern)(DecArgs) = primed ? (filter ? prior_decode_kernel<true, true> : prior_decode_kernel<true, false>)
-                                 : (filter ? prior_decode_kernel<false, true> : prior_decode_kernel<false, false>);
+  void (*kern)(DecArgs) =
+      primed ? (filter == 2 ? prior_decode_kernel<true, 2> : filter ? prior_decode_kernel<true, 1>
+                                                                    : prior_decode_kernel<true, 0>)
+             : (filter == 2 ? prior_decode_kernel<false, 2> : filter ? prior_decode_kernel<false, 1>
+                                                                     : prior_decode_kernel<false, 0>);
   hipLaunchKernelGGL(kern, dim3(N), dim3(256), 0, (hipStream_t)stream, a);
   VQA_LAUNCHED("prior_decode_kernel");
   return VQA_OK;
+}
+
+extern "C" int vqa_prior_decode_primed(const vqa_prior_layer* layers, int depth, const float* x_embedding,
+                                       const float* pos_embedding, const float* out_kernel, const float* out_bias,
+                                       const float* ycond, const float* xcond, const int64_t* forced, float* logits,
+                                       int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx,
+                                       int width, int heads, int blocks, int bins, int out_ld, int64_t start,
+                                       uint64_t seed, const int64_t* prime, int prime_len, float temperature,
+                                       int top_k, vqa_stream_t stream) {
+  return vqa_prior_decode_filtered(layers, depth, x_embedding, pos_embedding, out_kernel, out_bias, ycond, xcond, forced,
+                                   logits, tokens, cache, cache_bytes, N, steps, ctx, width, heads, blocks, bins, out_ld,
+                                   start, seed, prime, prime_len, temperature, top_k, 1.0f, nullptr, stream);
 }
 
 extern "C" int vqa_prior_decode(const vqa_prior_layer* layers, int depth, const float* x_embedding,

@@ -51,7 +51,7 @@ class VQVAESampler:
                                      device=device, seed=seed + l))
 
     def sample(self, n_samples, y_genre=None, seed=0, *, total_length=None, hop_lengths=None, temperature=1.0,
-               top_k=0):
+               top_k=0, top_p=1.0):
         """Sampler.py:65-114: from the top level down; returns [zs_0, ..., zs_{L-1}], (n_samples, codes_l) int64
         codes without the start token.
 
@@ -59,20 +59,20 @@ class VQVAESampler:
         seed + l. Otherwise long-form sampling: total_length counts top-level codes (at least the top n_ctx) and
         level l gets total_length * hop_top / hop_l codes, drawn in windows of n_ctx_l codes that start every
         hop_lengths[l] codes (default n_ctx_l // 2; window_starts). Each window is one primed decode launch, see
-        sample_level. temperature / top_k: as FMHABasedAutoregressiveModel.sample, for every window."""
+        sample_level. temperature / top_k / top_p: as FMHABasedAutoregressiveModel.sample, for every window."""
         dev = self.priors[0].device
         zs = [torch.zeros(n_samples, 0, dtype=torch.int64, device=dev) for _ in range(self.levels)]
         totals, hops = self._plan(total_length, hop_lengths)
         for level in reversed(range(self.levels)):
             zs = self.sample_level(zs, level, y_genre=y_genre, seed=seed, total_length=totals[level],
-                                   hop_length=hops[level], temperature=temperature, top_k=top_k)
+                                   hop_length=hops[level], temperature=temperature, top_k=top_k, top_p=top_p)
         return zs
 
     def sample_audio(self, n_samples, vqvae, y_genre=None, seed=0, *, level=0, chunk_codes=4096, gain=1.0,
                      **sample_kwargs):
         """sample() followed by the VQ-VAE's decoder, as the reference does after every sampling run
         (utils/tf_utils.py:196-226 generate_and_save_waves: model.decode(codes, level)): draws the codes of every
-        level (sample_kwargs: total_length, hop_lengths, temperature, top_k — the draw is sample()'s, seeds
+        level (sample_kwargs: total_length, hop_lengths, temperature, top_k, top_p — the draw is sample()'s, seeds
         included), then renders level `level`'s codes to 16-bit PCM in chunks of chunk_codes codes (VQVAE.render).
         Returns (pcm (n_samples, codes * hop) int16, clipped (n_samples,) int32, zs). The sampler and the VQ-VAE
         must have the same levels and hop lengths; codes outside the codebook — the start token of a prior whose
@@ -123,7 +123,7 @@ class VQVAESampler:
         return starts
 
     def sample_level(self, zs, level, y_genre=None, seed=0, total_length=None, hop_length=None, temperature=1.0,
-                     top_k=0):
+                     top_k=0, top_p=1.0):
         """Sampler.py:116-124 (a stub in the reference): draw level `level` given the levels above it in zs and
         return zs with that level filled. total_length: this level's codes (default one window), hop_length: the
         distance of its window starts (default n_ctx // 2).
@@ -144,7 +144,7 @@ class VQVAESampler:
             prime = z[:, s:] if z.shape[1] > s else None
             x_cond = pr.get_cond(zs, s, s + n_ctx)
             seq = pr.sample(n_samples=n_samples, z_cond=x_cond, y=y_genre, seed=seed + level + self.levels * w,
-                            prime=prime, temperature=temperature, top_k=top_k)
+                            prime=prime, temperature=temperature, top_k=top_k, top_p=top_p)
             z = torch.cat([z, seq[:, 1 + z.shape[1] - s:]], dim=-1)  # start token and prime removed
         zs[level] = z
         return zs
