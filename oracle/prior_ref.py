@@ -287,7 +287,7 @@ def train_step_grads(p, cfg: PriorConfig, codes, tf_mask, prefix="prior", x_cond
 
 
 def gumbel_uniform(seed: int, n: int, step: int, k: np.ndarray) -> np.ndarray:
-    """The product's counter-based uniform in (0, 1) for (sample n, step, bin k) (vqa_prior.hip prior_uniform):
+    """The product's counter-based uniform in (0, 1) for (sample n, step, bin k) (vqa_prior.h prior_uniform):
     splitmix64-style hash of (seed, n, step, k) -> 24 high bits -> (u + 0.5) / 2^24. numpy restatement."""
     M = np.uint64(0xFFFFFFFFFFFFFFFF)
 

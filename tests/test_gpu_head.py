@@ -1,4 +1,4 @@
-"""Kernel-level parity of the prior's fused head + cross entropy (vqa_prior.hip head_fwd_kernel, head_bwd_dx_kernel,
+"""Kernel-level parity of the prior's fused head + cross entropy (vqa_prior_head.hip head_fwd_kernel, head_bwd_dx_kernel,
 head_bwd_dw_kernel) past the shapes of tests/test_gpu_prior.py: weight-gradient segments of several 64-row chunks
 with a ragged last one (M from vqa_head_bwd_plan), M = 1, the vocabulary edges V = 64 and 65, targets at 0 and V - 1,
 head_fwd without targets, NaN guard bands on dx, lse and amax.

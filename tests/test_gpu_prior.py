@@ -1,4 +1,4 @@
-"""GPU parity of the factorized-attention prior (vqa_prior.hip through the C-ABI) against oracle/prior_ref.py.
+"""GPU parity of the factorized-attention prior (vqa_prior*.hip through the C-ABI) against oracle/prior_ref.py.
 
 Kernel level: the sequence-linear layer (causal 3-tap conv and Dense, data and weight gradients), the three
 attention factorizations (forward and backward vs fp64 autograd), the fused head + cross entropy. Model level:

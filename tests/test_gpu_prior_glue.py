@@ -1,4 +1,5 @@
-"""Direct checks of the prior's small glue kernels (vqa_prior.hip: colsum, axpy, rowsum, tf_mix, scale, dropout, embed),
+"""Direct checks of the prior's small glue kernels (vqa_prior.hip: colsum, axpy, tf_mix, scale, dropout, embed;
+vqa_prior_head.hip: rowsum),
 each against two lines of torch, including one case per grid-stride kernel with work just past the launch cap of
 8192 workgroups x 256 threads so that the second trip of the loop runs.
 

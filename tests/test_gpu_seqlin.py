@@ -1,4 +1,4 @@
-"""Kernel-level parity of the prior's sequence-linear family (vqa_prior.hip: seqlin_kernel, seqlin_d_kernel,
+"""Kernel-level parity of the prior's sequence-linear family (vqa_prior_seqlin.hip: seqlin_kernel, seqlin_d_kernel,
 seqlin_prep_kernel, seqlin_wgrad_kernel) against the plain fp64 reference of tests/prior_parity_ref.py, on every
 route launch_seqlin can choose. Each case asserts the route it means to check through vqa_seqlin_route /
 vqa_seqlin_wgrad_plan, writes into the middle of a NaN-filled buffer (guard rows and the padding columns of a

@@ -2,7 +2,7 @@
 tests/test_gpu_decode_top_p.py and tests/test_top_p_rows_host.py.
 
 DELTA, the margin inside which a row's kept set is not decided between the device and fp64 (a bin v with
-|A(lg[v]) - p Z| <= DELTA * Z), follows from the arithmetic written above dec_nucleus_threshold (csrc/vqa_prior.hip),
+|A(lg[v]) - p Z| <= DELTA * Z), follows from the arithmetic written above dec_nucleus_threshold (vqa_prior_decode.hip),
 with the same fp32 logits, temperature and p on both sides:
   * the exponent a = (lg - max) / T is one fp32 subtraction and one division: relative error <= 2^-23, so the
     weight exp(a) is off by a factor within 1 +- |a| 2^-23; expf adds at most 1 ulp (2^-23);

@@ -42,10 +42,19 @@ def notes(lib):
     return out
 
 
+def code(ins):
+    """A kernel's instructions without what pads the section behind it: "..." (llvm-objdump's elision of zero bytes) and
+    the s_nop / s_code_end run after the last instruction, whose length depends on what follows the kernel in its code
+    object (the last kernel of a unit carries the whole end-of-section pad), not on the kernel."""
+    ins = [i for i in ins if i != "..."]
+    while ins and ins[-1] in ("s_nop 0", "s_code_end"):
+        ins.pop()
+    return ins
+
+
 def main():
     old, new = sys.argv[1], sys.argv[2]
-    # "..." is llvm-objdump's elision of the zero padding behind a kernel (what follows it in the section), no code
-    ta, tb = ({k: [i for i in v if i != "..."] for k, v in kernel_diff.funcs(lib).items()} for lib in (old, new))
+    ta, tb = ({k: code(v) for k, v in kernel_diff.funcs(lib).items()} for lib in (old, new))
     na, nb = notes(old), notes(new)
     kernels = sorted(set(na) | set(nb))
     bad = 0

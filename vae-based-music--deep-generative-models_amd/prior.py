@@ -15,7 +15,7 @@ Reference classes kept here (same names, constructor arguments and call surface)
                                                    teacher_force_rate), loss/accuracy trackers, Keras Adam
   src/conditioner/label_conditioners.py:9-48     LabelConditioner (genre Embedding -> the start position)
 
-MI355X path (libvqa, vqa_prior.hip): every linear layer is the MFMA sequence-linear kernel (the causal conv is
+MI355X path (libvqa, vqa_prior*.hip): every linear layer is the MFMA sequence-linear kernel (the causal conv is
 its 3-tap form); attention is flash-style on MFMA for the row / prev-row blocks and a register kernel for the
 4-long columns; the output Dense is fused with the cross entropy / argmax so the (N, T, bins) logits are never
 written; sampling is ONE persistent kernel per batch that walks the positions with a key/value cache instead of

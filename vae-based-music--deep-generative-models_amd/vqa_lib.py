@@ -816,7 +816,7 @@ def stft_magnitude(x, mag, n_fft, hop, win):
     _check(lib().vqa_stft_magnitude(ptr(x), ptr(mag), B, T, n_fft, hop, win, stream()), "vqa_stft_magnitude")
 
 
-# ---- factorized-attention prior (vqa_prior.hip) -----------------------------------------------------
+# ---- factorized-attention prior (vqa_prior*.hip) ----------------------------------------------------
 def rptr(t: torch.Tensor):
     """(pointer, row stride) of a row-strided view (last dim contiguous, uniform row stride): column slices
     such as qkv[..., 0:32] of a (N, T, 96) tensor."""
