@@ -114,6 +114,27 @@ def test_captured_feed_step_equals_eager(corpus, eager):
     assert feed.step == 4
 
 
+@pytest.mark.parametrize("source", ["tensors", "feed"])
+def test_capture_warmup_and_the_host_step_counter(corpus, source):
+    """Prior._step (the checkpoint's "step") counts a warm-up step of capture_train_step only when the capture
+    draws from a feed; the optimizer counts every warm-up step either way, and a replay counts once. The feed's
+    device counter stands at 2 after the capture — the draw recorded into the graph is not executed, as
+    test_captured_feed_step_equals_eager has it for warmup=1 — and at 3 after the first replay."""
+    p, feed = _prior(), _feed(corpus)
+    example = feed if source == "feed" else tuple(torch.from_numpy(a).cuda() for a in feed.host_batch(0))
+    p.capture_train_step(example, warmup=2)
+    assert int(p.optimizer.iterations.item()) == 2
+    if source == "feed":
+        assert p._step == 2 and feed.step == 2
+    else:
+        assert p._step == 0 and feed.step == 0
+    before = p._step
+    p.train_step(example)                                   # a replay
+    torch.cuda.synchronize()
+    assert p._step == before + 1 and int(p.optimizer.iterations.item()) == 3
+    assert feed.step == (3 if source == "feed" else 0)
+
+
 def test_unconditioned_top_level_fit_and_evaluate(corpus):
     """The top level of two with 64 codes of context (its tracks hold 80, 64, 72 and 96)."""
     p = Prior(1, [(256,), (64,)], K, [3, 2], [2, 2], None, PK, None, dtype="fp32", device="cuda:0", seed=3)

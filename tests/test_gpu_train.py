@@ -345,6 +345,34 @@ def test_graph_replay_matches_eager(cuda):
             assert np.array_equal(sa[k], sb[k]), k
 
 
+def test_replay_after_eager_test_step(cuda):
+    """An eager test_step between capture and replay: the replay puts the exchange form the graphs were captured
+    around (_graph_overlapped) back into _overlapped, which an eager step rewrites with its own and _exchange /
+    _update read, and the replayed step leaves the state bitwise equal to the same sequence run eagerly."""
+    c = CONFIGS["tiny"]
+    cfg, B = c["cfg"], c["B"]
+    params, vq = R.init_params(cfg, 1), R.init_vq_state(cfg, 2)
+    xs = [R.synthetic_batch(B, cfg.input_len, seed=40 + i) for i in range(3)]
+    a = _model(cfg, B, "fp32", params, vq)
+    a.train_step(xs[0])
+    a.test_step(xs[1])
+    a.train_step(xs[2])
+    b = _model(cfg, B, "fp32", params, vq)
+    b.capture_train_step(xs[0], warmup=1)    # one real eager step on xs[0]
+    b.test_step(xs[1])
+    assert b._overlapped is False and b._graph_overlapped is False    # one device: no exchange to overlap
+    b._overlapped = True                     # what an eager step with the per-level exchange leaves behind
+    b.train_step(xs[2])                      # a replay
+    torch.cuda.synchronize()
+    assert b._graph is not None and b._overlapped == b._graph_overlapped
+    assert torch.equal(a.store.flat, b.store.flat)
+    assert torch.equal(a.optimizer.m, b.optimizer.m) and torch.equal(a.optimizer.v, b.optimizer.v)
+    for sa, sb in zip(a.get_vq_state(), b.get_vq_state()):
+        assert sa["calls"] == sb["calls"]
+        for k in ("embeddings", "m_t", "N_t"):
+            assert np.array_equal(sa[k], sb[k]), k
+
+
 def test_call_encode_decode_test_step(cuda):
     c = CONFIGS["tiny"]
     cfg, B = c["cfg"], c["B"]

@@ -36,8 +36,9 @@ from code_feed import CodeFeed
 from conditioners import ConditionerNet
 from vqa_layers import CKPT_VERSION, ParamStore, checkpoint_layout
 from vqa_metrics import Mean
-from vqa_module import keras_evaluate
+from vqa_module import keras_evaluate, keras_fit_feed
 from vqa_optim import Adam
+from vqa_train import CapturedStep, adam_from_checkpoint, adam_state, set_adam_state
 
 
 def create_look_ahead_mask(q_len, k_len):
@@ -676,8 +677,11 @@ class Prior:
         self.train_monitor = prior_monitor
         self.teacher_seed = 3
         self._step = 0
-        self._graph = None
-        self._graph_feed = None  # the CodeFeed a captured step draws from (None: it copies the caller's codes in)
+        self._captured: Optional[CapturedStep] = None
+
+    # None or the captured (g1, g2), g2 None in the one-graph form; the CodeFeed the step draws from (None: a copy-in)
+    _graph = property(lambda self: self._captured and self._captured.graphs)
+    _graph_feed = property(lambda self: self._captured and self._captured.feed)
 
     @property
     def metrics(self):
@@ -690,8 +694,7 @@ class Prior:
         device each step. A captured step is dropped (it holds the previous optimizer's buffers)."""
         self.optimizer = optimizer or Adam()
         self.optimizer.build(self.prior.store)
-        self._graph = None
-        self._graph_feed = None
+        self._captured = None
 
     def reset_metrics(self):
         for m in self.metrics:
@@ -766,9 +769,6 @@ class Prior:
         return {"loss": loss, "perplexity(per word)": torch.exp(loss), "accuracy": self.train_accuracy_tracker.result()}
 
     # -------------------------------------------------------------- the step
-    def _world(self):
-        return vqa_dp.world_size(self.process_group)
-
     def _label_embed(self, y):
         """LabelConditioner(y) (label_conditioners.py:26-45) as the (N, width) fp32 rows the embedding kernel puts at
         position 0."""
@@ -859,7 +859,7 @@ class Prior:
 
     def _apply(self):
         """Keras Adam on the (rank-mean) gradients, then the trackers on the global means."""
-        w = self._world()
+        w = vqa_dp.world_size(self.process_group)
         self.optimizer.apply(self.prior.store, grad_scale=1.0 / w)
         self.train_loss_tracker.update_state(self._scalars[0] / w)
         self.train_accuracy_tracker.update_state(self._scalars[1] / w)
@@ -867,13 +867,12 @@ class Prior:
     def train_step(self, x, teacher_force_rate=0.2, tf_mask=None):
         """prior.py:241-335. tf_mask (N, T) bool overrides the random teacher-forcing draw (parity tests)."""
         # the captured graph bakes in its teacher-forcing rate: another rate (e.g. a schedule) runs eagerly
-        replayable = (self._graph is not None and tf_mask is None
+        replayable = (self._captured is not None and tf_mask is None
                       and float(teacher_force_rate) == self._graph_rate)
-        if replayable and self._graph_feed is not None:
-            # the step captured with this very feed draws its batch inside the graph; any other feed (or the same
-            # one after a change of seed, which the graph's launch does not see) and tensors run eagerly below —
-            # the graph's inputs are the feed's buffers, which a replay overwrites
-            if x is self._graph_feed and x.seed == self._graph_feed_seed:
+        if replayable and self._captured.feed is not None:
+            # the step captured with this very feed draws its batch inside the graph; any other feed and tensors run
+            # eagerly below — the graph's inputs are the feed's buffers, which a replay overwrites
+            if self._captured.draws_from(x):
                 self._check_feed(x)
                 self._replay()
                 return self.results()
@@ -894,11 +893,7 @@ class Prior:
         return self.results()
 
     def _replay(self):
-        g1, g2 = self._graph
-        g1.replay()
-        if g2 is not None:
-            self._exchange()
-            g2.replay()
+        self._captured.replay()
         self._step += 1
 
     def _graph_fits(self, codes, upper, y):
@@ -978,44 +973,22 @@ class Prior:
         head of the first graph and the graph's inputs are the feed's own buffers (no copy); the warm-up steps are
         real steps on the feed's next batches, and a later train_step(feed) with this feed replays."""
         feed = codes_example if isinstance(codes_example, CodeFeed) else None
-        self._graph = None
+        self._captured = None
         if feed is not None:
             self._check_feed(feed)
             self._graph_in = self._feed_inputs(feed)
         else:
             codes, upper, y = self._codes(codes_example)
             self._graph_in = tuple(None if t is None else t.clone() for t in (codes, upper, y))
-        self._graph_feed, self._graph_feed_seed = feed, (feed.seed if feed is not None else None)
         c, u, l = self._graph_in
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                if feed is not None:
-                    feed.next()
-                self._compute(c, u, teacher_force_rate, None, l)
-                self._exchange()
-                self._apply()
-                if feed is not None:
-                    self._step += 1
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
-        pool = torch.cuda.graph_pool_handle()
-        g1 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1, pool=pool, capture_error_mode="thread_local"):
-            if feed is not None:
-                feed.next()
-            self._compute(c, u, teacher_force_rate, None, l)
-            if not vqa_dp.active(self.process_group):
-                self._apply()
-        g2 = None
-        if vqa_dp.active(self.process_group):  # two graphs around the eager all_reduce
-            g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2, pool=pool, capture_error_mode="thread_local"):
-                self._apply()
-        self._graph = (g1, g2)
+        step = CapturedStep(self.device, self.process_group, feed,
+                            lambda: self._compute(c, u, teacher_force_rate, None, l), self._exchange, self._apply)
+        step.warm_up(warmup)
+        if feed is not None:
+            self._step += warmup  # only a feed's warm-up steps count: kept for bitwise continuity of checkpoints
+        step.capture()
+        self._captured = step
         self._graph_rate = float(teacher_force_rate)
-        torch.cuda.synchronize(self.device)
 
     def fit(self, x, epochs=1, teacher_force_rate=0.2, verbose=0):
         """Minimal keras fit over a code_feed.CodeFeed: the trackers reset per epoch (keras semantics), an epoch is
@@ -1024,15 +997,7 @@ class Prior:
         if not isinstance(x, CodeFeed):
             raise ValueError("Prior.fit trains from a code_feed.CodeFeed")
         self._check_feed(x)
-        hist = []
-        for ep in range(epochs):
-            self.reset_metrics()
-            for _ in range(x.steps_per_epoch):
-                self.train_step(x, teacher_force_rate=teacher_force_rate)
-            hist.append({k: float(v) for k, v in self.results().items()})
-            if verbose:
-                print(f"epoch {ep + 1}/{epochs}", hist[-1])
-        return hist
+        return keras_fit_feed(self, x, epochs, verbose, teacher_force_rate=teacher_force_rate)
 
     # -------------------------------------------------------------- checkpoint
     def save(self, path: str):
@@ -1047,9 +1012,7 @@ class Prior:
                "config": {"level": self.level, "bins": self.bins, "context_length": self.context_length,
                           "width": self.prior.d_model, "depth": self.prior.depth, "heads": self.prior.heads,
                           "blocks": self.prior.blocks, "genre_classes": self.genre_bins},
-               "weights": st.flat.detach().cpu().clone(),
-               "adam_m": self.optimizer.m.detach().cpu().clone(), "adam_v": self.optimizer.v.detach().cpu().clone(),
-               "iterations": int(self.optimizer.iterations.item()), "step": int(self._step),
+               "weights": st.flat.detach().cpu().clone(), **adam_state(self.optimizer), "step": int(self._step),
                "trackers": torch.stack([t._acc.detach().cpu() for t in self.metrics])}
         torch.save(out, path)
 
@@ -1060,9 +1023,7 @@ class Prior:
         st = self.prior.store
         lay = checkpoint_layout(ck, st, "prior", path)
         st.flat.copy_(st.from_layout(ck["weights"], lay, path).to(self.device))
-        self.optimizer.m.copy_(st.from_layout(ck["adam_m"], lay, f"{path} (adam_m)").to(self.device))
-        self.optimizer.v.copy_(st.from_layout(ck["adam_v"], lay, f"{path} (adam_v)").to(self.device))
-        self.optimizer.iterations.fill_(int(ck["iterations"]))
+        set_adam_state(self.optimizer, adam_from_checkpoint(ck, st, lay, path), self.device)
         self._step = int(ck["step"])
         for t, acc in zip(self.metrics, ck["trackers"]):
             t._acc.copy_(acc.to(self.device))

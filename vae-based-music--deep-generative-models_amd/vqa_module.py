@@ -58,6 +58,20 @@ def _is_array(a) -> bool:
     return isinstance(a, (torch.Tensor, np.ndarray))
 
 
+def keras_fit_feed(model, feed, epochs=1, verbose=0, **train_step_kwargs):
+    """keras Model.fit over a device feed (AudioFeed, CodeFeed): the metrics reset per epoch, an epoch is the feed's
+    steps_per_epoch calls of model.train_step(feed, **train_step_kwargs); returns the epoch-end results as floats."""
+    hist = []
+    for ep in range(epochs):
+        model.reset_metrics()
+        for _ in range(feed.steps_per_epoch):
+            model.train_step(feed, **train_step_kwargs)
+        hist.append({k: float(v) for k, v in model.results().items()})
+        if verbose:
+            print(f"epoch {ep + 1}/{epochs}", hist[-1])
+    return hist
+
+
 def keras_evaluate(model, x=None, y=None, batch_size=None, verbose=0, steps=None, return_dict=False):
     """keras Model.evaluate (TF 2.7 semantics) over `model.test_step`, as the reference's monitors call it
     (src/callback/vae_monitor.py:69, src/callback/monitors.py:81: `self.model.evaluate(self.val_dataset)`):

@@ -36,8 +36,9 @@ from data_utils import SpectralTarget, multispectral_loss_and_grad
 from encdec import Decoder, Encoder
 from vqa_layers import CKPT_VERSION, ParamStore, checkpoint_layout
 from vqa_metrics import SlotMean
-from vqa_module import keras_evaluate
+from vqa_module import keras_evaluate, keras_fit_feed
 from vqa_optim import Adam
+from vqa_train import CapturedStep, adam_from_checkpoint, adam_state, set_adam_state
 from VectorQuantizer import VectorQuantizer
 
 
@@ -256,8 +257,7 @@ class VQVAE:
         self.optimizer: Optional[Adam] = None
         self.vqvaes = [LevelModel(self.input_shape, self.encoders[l], self.decoders[l], self.vqs[l], l, owner=self)
                        for l in range(levels)]
-        self._graph = None
-        self._graph_feed = None  # the AudioFeed a captured step draws from (None: it copies the caller's batch in)
+        self._captured: Optional[CapturedStep] = None
         # run the levels' independent forward/backward chains on one stream each (VQA_LEVEL_STREAMS=0: serial)
         self.concurrent_levels = os.environ.get("VQA_LEVEL_STREAMS", "1") != "0"
         self._streams = None
@@ -271,9 +271,11 @@ class VQVAE:
         is dropped: it holds the previous optimizer's buffers (m, v, step counter, learning rate)."""
         self.optimizer = optimizer or Adam()
         self.optimizer.build(self.store)
-        self._graph = None
-        self._graph_pool = None
-        self._graph_feed = None
+        self._captured = None
+
+    # None or the captured (g1, g2), g2 None in the one-graph form; the AudioFeed the step draws from (None: a copy-in)
+    _graph = property(lambda self: self._captured and self._captured.graphs)
+    _graph_feed = property(lambda self: self._captured and self._captured.feed)
 
     @property
     def metrics(self):
@@ -302,12 +304,6 @@ class VQVAE:
         if tuple(x.shape[1:]) != (self.T, self.channels):
             raise ValueError(f"input shape {tuple(x.shape)} does not match keras.Input{(self.T, self.channels)}")
         return x.contiguous()
-
-    def _world(self) -> int:
-        return vqa_dp.world_size(self.process_group)
-
-    def _rank(self) -> int:
-        return vqa_dp.rank(self.process_group)
 
     # ------------------------------------------------------------------ the step
     def _compute(self, x: torch.Tensor, training_grads: bool):
@@ -411,7 +407,7 @@ class VQVAE:
             vq.apply_ema(update_trackers=False)  # after every use of the old codebook in this level
 
     def _update(self, apply_grads: bool):
-        world = self._world()
+        world = vqa_dp.world_size(self.process_group)
         if apply_grads:
             self.optimizer.apply(self.store, grad_scale=1.0 / world)
         if (vqa_dp.active(self.process_group) and not self._overlapped) or self._r3_layout:
@@ -468,15 +464,14 @@ class VQVAE:
         if self.optimizer is None:
             self.compile()
         if isinstance(data, AudioFeed):
-            # the step captured with this very feed draws its batch inside the graph; any other feed (or the same
-            # one after a change of seed, which the graph's launch does not see) is drawn here and runs eagerly
-            if self._graph is not None and data is self._graph_feed and data.seed == self._graph_feed_seed:
+            # the step captured with this very feed draws its batch inside the graph; any other is drawn here
+            if self._captured is not None and self._captured.draws_from(data):
                 self._replay()
                 return self.results()
             data = data.next()
         x = self._as_input(data)
         # a graph captured with a feed overwrites its input with the feed's batch: other data runs eagerly
-        if self._graph is not None and self._graph_feed is None and x.shape == self._graph_x.shape:
+        if self._captured is not None and self._captured.feed is None and x.shape == self._graph_x.shape:
             self._graph_x.copy_(x)
             self._replay()
             return self.results()
@@ -521,54 +516,25 @@ class VQVAE:
                 raise ValueError("the feed's batch buffer must be on the model's device")
         else:
             self._graph_x = self._as_input(x_example).clone()
-        self._graph = None
-        self._graph_feed, self._graph_feed_seed = feed, (feed.seed if feed is not None else None)
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                if feed is not None:
-                    feed.next()
-                self._compute(self._graph_x, True)
-                self._exchange()
-                self._update(True)
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        torch.cuda.synchronize(self.device)
+        self._captured = None
+        step = CapturedStep(self.device, self.process_group, feed, lambda: self._compute(self._graph_x, True),
+                            self._exchange, lambda: self._update(True))
+        step.warm_up(warmup)
         if self.overlap_exchange and vqa_dp.active(self.process_group) and vqa_dp.device_side(self.process_group):
             # the direct-RCCL issuer (and, if the group made it lazily, its communicator) exists before the capture
             vqa_dp.rccl_direct(self.process_group, self.device)
-        self._graph_pool = torch.cuda.graph_pool_handle()
-        g1 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1, pool=self._graph_pool, capture_error_mode="thread_local"):
-            if feed is not None:
-                feed.next()
-            self._compute(self._graph_x, True)
-            one_graph = self._overlapped or not vqa_dp.active(self.process_group)
-            if self._overlapped:
-                self._exchange()
-            if one_graph:
-                self._update(True)
-        g2 = None
-        if not one_graph:
-            g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2, pool=self._graph_pool, capture_error_mode="thread_local"):
-                self._update(True)
-        self._graph = (g1, g2)
+        # _compute sets _overlapped (_overlap_now): only then are its collectives and the losses' exchange captured
+        step.capture(exchange_captured=lambda: self._overlapped)
+        self._captured = step
         # the exchange form the graphs were captured around, fixed here: an eager step in between (test_step,
         # evaluate) rewrites self._overlapped with ITS form
         self._graph_overlapped = self._overlapped
-        torch.cuda.synchronize(self.device)
 
     def _replay(self):
-        g1, g2 = self._graph
         self._overlapped = self._graph_overlapped
-        g1.replay()
-        if g2 is not None:
-            # split graphs: the whole bucket is exchanged between them (the per-level collectives are captured only
-            # in the one-graph form)
-            assert not self._graph_overlapped
-            self._exchange()
-            g2.replay()
+        # the per-level collectives are captured only in the one-graph form: split graphs exchange the whole bucket
+        assert self._graph[1] is None or not self._graph_overlapped
+        self._captured.replay()
 
     # ------------------------------------------------------------------ inference API
     def _level_forward_only(self, x, l, training):
@@ -753,15 +719,7 @@ class VQVAE:
         if self.optimizer is None:
             self.compile()
         if isinstance(x, AudioFeed):
-            hist = []
-            for ep in range(epochs):
-                self.reset_metrics()
-                for _ in range(x.steps_per_epoch):
-                    self.train_step(x)
-                hist.append({k: float(v) for k, v in self.results().items()})
-                if verbose:
-                    print(f"epoch {ep + 1}/{epochs}", hist[-1])
-            return hist
+            return keras_fit_feed(self, x, epochs, verbose)
         xs = np.asarray(x, np.float32)
         n = xs.shape[0]
         rng = np.random.default_rng(seed)
@@ -798,8 +756,7 @@ class VQVAE:
         """Checkpoint payload: weights, Adam moments and step, VQ state."""
         sd = {"weights": self.store.flat.detach().cpu().clone(), "vq": self.get_vq_state()}
         if self.optimizer is not None and self.optimizer.m is not None:
-            sd.update({"adam_m": self.optimizer.m.cpu().clone(), "adam_v": self.optimizer.v.cpu().clone(),
-                       "iterations": int(self.optimizer.iterations.item())})
+            sd.update(adam_state(self.optimizer))
         return sd
 
     def save(self, path: str):
@@ -835,11 +792,8 @@ class VQVAE:
         sd = {"weights": self.store.from_layout(ck["weights"], lay, path),
               "vq": [{k: ck[f"vq{l}/{k}"].numpy() for k in ("embeddings", "m_t", "N_t")}
                      | {"calls": ck[f"vq{l}/calls"]} for l in range(self.levels)]}
-        for k in ("adam_m", "adam_v"):
-            if k in ck:
-                sd[k] = self.store.from_layout(ck[k], lay, f"{path} ({k})")
-        if "iterations" in ck:
-            sd["iterations"] = ck["iterations"]
+        if "adam_m" in ck:
+            sd.update(adam_from_checkpoint(ck, self.store, lay, path))
         self.load_state_dict(sd)
 
     def load_state_dict(self, sd):
@@ -848,6 +802,4 @@ class VQVAE:
         if "adam_m" in sd:
             if self.optimizer is None:
                 self.compile()
-            self.optimizer.m.copy_(sd["adam_m"].to(self.device))
-            self.optimizer.v.copy_(sd["adam_v"].to(self.device))
-            self.optimizer.iterations.fill_(int(sd["iterations"]))
+            set_adam_state(self.optimizer, sd, self.device)
