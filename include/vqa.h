@@ -213,7 +213,8 @@ int vqa_dtail_bwd(const float* dy, const void* h, const float* w_up, const float
 /* e_sqnorm[k] = sum_d E[d][k]^2  (VectorQuantizer.py:180). E is (D, K). */
 int vqa_vq_sqnorm(const float* E, float* e_sqnorm, int D, int K, vqa_stream_t stream);
 /* idx[n] = argmin_k (sum_d z[n][d]^2 + e_sqnorm[k]) - 2 * (z @ E)[n][k]; ties -> lowest k.
- * Replaces get_code_indices, VectorQuantizer.py:170-186. min_dist nullable. z is (N, D) in dtype. */
+ * Replaces get_code_indices, VectorQuantizer.py:170-186. z is (N, D) in dtype. min_dist (nullable, a diagnostic the
+ * train step does not ask for): |z_n - e_idx[n]|^2 summed directly in fp32, +inf for a row with no finite distance. */
 int vqa_vq_argmin(const void* z, const float* E, const float* e_sqnorm, int64_t* idx, float* min_dist,
                   int64_t N, int D, int K, int dtype, vqa_stream_t stream);
 /* The same argmin for bf16 z (D in {32, 64}) on bf16 MFMA: E3 (K, 3, D) bf16 holds hi, mid, lo planes with

@@ -5,12 +5,21 @@ every parameter gradient against fp64 autograd (fp32: per-tensor relative L2 <= 
 rounding of 0 can take the other ReLU branch, see test_gpu_train — and median <= 1e-5; bf16: direction and
 overall magnitude, see the test), the LayerNorm and
 Embedding kernels alone strictly, the Embedding gradient bit-identical to its fixed summation order, repeated
-backward bitwise identical."""
+backward bitwise identical.
+
+test_layernorm_per_element judges every element (relative to max |ref|, tests/vqvae_parity_ref.py) instead of an L2
+ratio over the tensor, which one wrong lane or row cannot move (tests/test_vqvae_parity_host.py), at every
+vectorised width (64, 128, 256), past the forward kernels' launch caps (2048 workgroups of the vectorised kernels:
+32,768 / 16,384 / 8,192 rows a trip at C = 64 / 128 / 256; 4096 x 4 rows of the generic one) and at the backward's cap
+of 512 workgroups with empty trailing ones. y and dx: 1e-5 (fp32) / 1e-2 (bf16) or 8 * e32; dgamma and dbeta, fp32
+sums in both dtypes: 1e-5 or 8 * e32. Worst observed err / bound (MI355X, profiles/vqvae_kernel_parity.txt):
+y 0.30, dx 0.28, dgamma 0.13, dbeta 0.014."""
 import numpy as np
 import pytest
 import torch
 
 import vqa_lib as V
+import vqvae_parity_ref as R
 from conditioners import ConditionerNet
 from oracle import conditioner_ref as CR
 
@@ -188,3 +197,61 @@ def test_embedding_kernels_exact(cuda):
     assert torch.equal(res[0], res[1])
     want, _ = _fixed_order_sums(dy[ok].numpy(), idx[ok].numpy(), K)
     assert np.array_equal(res[0].numpy(), want)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("C,rows", [(256, 16384 + 5), (128, 32768 + 3), (64, 65536 + 9), (96, 16384 + 3), (65, 7),
+                                    (1, 5), (1000, 3), (1024, 2), (128, 1)])
+def test_layernorm_per_element(cuda, C, rows, dtype):
+    """Row 0 is constant (variance 0: y = beta exactly in fp32), row 1 = 1000 + 1e-2 randn (mean >> spread), dy's
+    rows next to a 64-row edge carry 8x the weight. (128, 32768 + 3): the backward runs 512 workgroups of 65 rows,
+    the last 7 of them with an empty range."""
+    x, gamma, beta, dy = R.ln_inputs(C, rows, dtype)
+    want_y = R.ln_fwd(x.double(), gamma.double(), beta.double())
+    want_b = R.ln_bwd(x.double(), dy.double(), gamma.double())
+    e_y = R.e32_of(R.ln_fwd, x, gamma, beta)
+    e_b = R.e32_of(R.ln_bwd, x, dy, gamma)
+    xd, dyd, gd, bd = x.cuda(), dy.cuda(), gamma.cuda(), beta.cuda()
+    ybuf, y = R.guarded((rows, C), dtype, cuda)
+    V.layernorm_fwd(xd, gd, bd, y, 1e-6)
+    runs = []
+    for _ in range(2):
+        outs = [R.guarded((rows, C), dtype, cuda), R.guarded((C,), torch.float32, cuda),
+                R.guarded((C,), torch.float32, cuda)]
+        V.layernorm_bwd(xd, dyd, gd, outs[0][1], outs[1][1], outs[2][1], 1e-6)
+        torch.cuda.synchronize()
+        assert R.guards_intact(ybuf, y) and all(R.guards_intact(b, v) for b, v in outs)
+        runs.append([v.cpu() for _, v in outs])
+    assert all(torch.equal(a, b) for a, b in zip(*runs))          # the partial order is fixed
+    if dtype == torch.float32:
+        assert torch.equal(y[0].cpu(), beta)
+    case = f"{str(dtype)[6:]} C{C} rows{rows}"
+    P = R.LN_TOL[dtype]
+    checks = [("ln_y", y, want_y, R.bound(P, e_y), e_y), ("ln_dx", runs[0][0], want_b[0], R.bound(P, e_b[0]), e_b[0]),
+              ("ln_dgamma", runs[0][1], want_b[1], R.bound(R.LN_WGRAD_TOL, e_b[1]), e_b[1]),
+              ("ln_dbeta", runs[0][2], want_b[2], R.bound(R.LN_WGRAD_TOL, e_b[2]), e_b[2])]
+    errs = []
+    for group, got, want, tol, e32 in checks:
+        err = R.rel(got.float(), want)
+        R.record(group, case, e32, tol, err)
+        errs.append((group, err, tol))
+    bad = [c for c in errs if not c[1] < c[2]]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_embedding_fwd_past_the_launch_cap(cuda, dtype):
+    """N (D / 4) = 1,048,586 float4 pieces against 4096 x 256 = 1,048,576 a trip; out-of-range indices (-1, K, K + 5,
+    the last one in the second trip) give zero rows."""
+    D, K, N = 8, 12, 524288 + 5
+    g = R.gen(N)
+    table = torch.randn(K, D, generator=g)
+    idx = torch.randint(0, K, (N,), generator=g)
+    idx[0], idx[77], idx[-2] = -1, K, K + 5
+    ok = (idx >= 0) & (idx < K)
+    ref = torch.where(ok[:, None], table[idx.clamp(0, K - 1)], torch.zeros(()))
+    obuf, out = R.guarded((N, D), dtype, cuda)
+    V.embedding_fwd(table.cuda(), idx.cuda(), out)
+    torch.cuda.synchronize()
+    assert R.guards_intact(obuf, out)
+    assert torch.equal(out.cpu(), ref.to(dtype))

@@ -53,3 +53,17 @@ def test_feed_deterministic_per_seed_and_rank(cuda):
     # a prefix of a longer chunk is the shorter chunk (draws keyed by sample index)
     e = synthetic_batch_device(4, 20000, seed=7, rank=0, device=cuda)
     assert torch.equal(e[:, :10000], a)
+
+
+def test_feed_prefix_past_the_launch_cap(cuda):
+    """synth_kernel runs at most 1024 workgroups x 256 threads per item: 262,144 samples a trip. T = 262,144 + 300
+    takes a second trip for the last 300 samples: they repeat bitwise, the head is the head of a short chunk (draws are
+    keyed by the sample index, not by the trip), and every value is finite and clipped."""
+    B, T = 2, 262144 + 300
+    a = synthetic_batch_device(B, T, seed=7, rank=0, device=cuda).cpu()
+    b = synthetic_batch_device(B, T, seed=7, rank=0, device=cuda).cpu()
+    short = synthetic_batch_device(B, 1000, seed=7, rank=0, device=cuda).cpu()
+    assert torch.equal(a[:, :1000], b[:, :1000]) and torch.equal(a[:, -300:], b[:, -300:])
+    assert torch.equal(a[:, :1000], short)
+    assert bool(torch.isfinite(a).all()) and float(a.abs().max()) <= 1.0
+    assert float(a[:, -300:].abs().max()) > 0.1     # the second trip wrote a signal, not zeros

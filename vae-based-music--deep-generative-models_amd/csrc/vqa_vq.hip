@@ -363,6 +363,33 @@ __global__ __launch_bounds__(256) void vq_split3_kernel(const float* E, bf16* E3
   o[2 * D] = lo;
 }
 
+// min_dist, the argmin entry points' optional diagnostic output: |z_n - e_k|^2 of the chosen code k = idx[n], summed
+// directly in fp32 (one thread per row; the train step never asks for it). The form the argmin compares,
+// (|z|^2 + |e|^2) - 2 z.e, is right for ranking codes but cancels: its absolute error is a few ulps of |z|^2 + |e|^2
+// (6e-5 at D = 64 with unit-variance data), as large as the distance itself for a row that sits on its code.
+// SPLIT: e from the bf16 planes, (hi + mid) + lo = E exactly. A row with no finite distance reports +inf.
+template <class T, bool SPLIT>
+__global__ __launch_bounds__(256) void vq_min_dist_kernel(const T* z, const float* E, const bf16* E3,
+                                                         const int64_t* idx, float* mind, long long N, int D, int K) {
+  const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const int64_t kv = idx[n];
+  const long long k = kv < 0 ? 0 : (kv >= K ? K - 1 : kv);  // the argmin kernels write [0, K); never index outside
+  float s = 0.f;
+  for (int d = 0; d < D; ++d) {
+    float e;
+    if (SPLIT) {
+      const bf16* p = E3 + (size_t)k * 3 * D + d;
+      e = ((float)p[0] + (float)p[D]) + (float)p[2 * D];
+    } else {
+      e = E[(long long)d * K + k];
+    }
+    const float diff = ld(z + n * D + d) - e;
+    s += diff * diff;
+  }
+  mind[n] = s < __builtin_inff() ? s : __builtin_inff();
+}
+
 // generic argmin (any D): one thread per row
 template <class T>
 __global__ __launch_bounds__(256) void vq_argmin_direct_kernel(const T* z, const float* E, const float* esq,
@@ -845,8 +872,9 @@ extern "C" int vqa_vq_sqnorm(const float* E, float* e_sqnorm, int D, int K, vqa_
 }
 
 template <class T>
-static int launch_argmin(const void* z, const float* E, const float* esq, int64_t* idx, float* mind, long long N,
+static int launch_argmin(const void* z, const float* E, const float* esq, int64_t* idx, float* min_dist, long long N,
                          int D, int K, hipStream_t s) {
+  float* const mind = nullptr;  // the argmin kernels' own distance-form value is not reported (vq_min_dist_kernel)
   const dim3 g((unsigned)((N + 127) / 128));
   switch (D) {
     case 4: hipLaunchKernelGGL((vq_argmin_mfma_kernel<T, 4>), g, dim3(256), 0, s, (const T*)z, E, esq, idx, mind, N, K); break;
@@ -859,6 +887,11 @@ static int launch_argmin(const void* z, const float* E, const float* esq, int64_
                          esq, idx, mind, N, D, K);
   }
   VQA_LAUNCHED("vq_argmin");
+  if (min_dist) {
+    hipLaunchKernelGGL((vq_min_dist_kernel<T, false>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const T*)z, E,
+                       (const bf16*)nullptr, idx, min_dist, N, D, K);
+    VQA_LAUNCHED("vq_min_dist_kernel");
+  }
   return VQA_OK;
 }
 
@@ -897,16 +930,22 @@ extern "C" int vqa_vq_argmin_split(const void* z, const void* E3, const float* e
     hipLaunchKernelGGL(vq_argmin_init_kernel, dim3(nb), dim3(256), 0, s, idx, (long long)N);
     VQA_LAUNCHED("vq_argmin_init_kernel");
   }
+  float* const none = nullptr;  // the kernels' own |z|^2 - 2 key is not reported (vq_min_dist_kernel)
   if (D == 64)
     hipLaunchKernelGGL(vq_argmin_split_kernel<64>, g, dim3(256), 0, s, (const bf16*)z, (const bf16*)E3, e_sqnorm, idx,
-                       min_dist, (long long)N, K, kspan);
+                       none, (long long)N, K, kspan);
   else
     hipLaunchKernelGGL(vq_argmin_split_kernel<32>, g, dim3(256), 0, s, (const bf16*)z, (const bf16*)E3, e_sqnorm, idx,
-                       min_dist, (long long)N, K, kspan);
+                       none, (long long)N, K, kspan);
   VQA_LAUNCHED("vq_argmin_split_kernel");
   if (nsplit > 1) {
-    hipLaunchKernelGGL(vq_argmin_unpack_kernel, dim3(nb), dim3(256), 0, s, idx, min_dist, (long long)N);
+    hipLaunchKernelGGL(vq_argmin_unpack_kernel, dim3(nb), dim3(256), 0, s, idx, none, (long long)N);
     VQA_LAUNCHED("vq_argmin_unpack_kernel");
+  }
+  if (min_dist) {
+    hipLaunchKernelGGL((vq_min_dist_kernel<bf16, true>), dim3(nb), dim3(256), 0, s, (const bf16*)z,
+                       (const float*)nullptr, (const bf16*)E3, idx, min_dist, (long long)N, D, K);
+    VQA_LAUNCHED("vq_min_dist_kernel");
   }
   return VQA_OK;
 }
