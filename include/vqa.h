@@ -709,6 +709,35 @@ int vqa_prior_decode_filtered(const vqa_prior_layer* layers, int depth, const fl
                               int heads, int blocks, int bins, int out_ld, int64_t start, uint64_t seed,
                               const int64_t* prime, int prime_len, float temperature, int top_k, float top_p,
                               int32_t* kept, vqa_stream_t stream);
+/* vqa_prior_decode_filtered with the log-probability of every written token (vqa_prior_decode_filtered forwards here
+ * with NULL, NULL and launches what it launched before).
+ * logp_model, logp_draw: (N, steps) fp32 each, either may be NULL. For step i of sample n let tok = tokens[n][i+1]
+ * (the drawn token, or the prime's on a primed step; with `forced` still the drawn one, not the forced input) and
+ * lg[0 .. bins) the step's logits:
+ *   logp_model[n][i] = lg[tok] - log sum_{v < bins} exp(lg[v])
+ *     the model's distribution: temperature 1, every bin; independent of temperature, top_k and top_p;
+ *   logp_draw[n][i]  = lg[tok] / T - log sum_{v in K} exp(lg[v] / T)
+ *     K = the bins that took part in the draw (after top-k and top-p: the set `kept` counts). With the filters off it
+ *     equals logp_model bitwise. -inf when tok is not in K: only on a primed step whose head runs, when the prime's
+ *     token was filtered out.
+ * On a primed step whose head is skipped (a prime without `logits`) both are 0.0f, as `kept` is 0: the sum over the
+ * steps is the log-likelihood of what was drawn, and the windows of long-form sampling add up without double
+ * counting. Asking for log-probabilities does not make the head run on primed steps; only `logits` does.
+ * The zero-padded columns bins .. out_ld enter neither sum.
+ * fp32 with the row maximum subtracted first, (lg - max) / T (the top bin is always in K: one maximum serves both
+ * sums); each of the 256 threads adds its bins in index order and the partial sums are combined by a fixed tree, no
+ * float atomics: a value is bitwise the same from run to run. Within 1e-5 of the exact value while
+ * |lg[tok] - max| / T <= 32 (the rounding argument is above dec_score_max, vqa_prior_decode.hip).
+ * The sums run in a kernel instantiation of their own, launched only when one of the two outputs is given; tokens
+ * and kept are bitwise what vqa_prior_decode_filtered gives.
+ * VQA_E_INVALID_ARG before any launch: what vqa_prior_decode_filtered rejects. */
+int vqa_prior_decode_scored(const vqa_prior_layer* layers, int depth, const float* x_embedding,
+                            const float* pos_embedding, const float* out_kernel, const float* out_bias,
+                            const float* ycond, const float* xcond, const int64_t* forced, float* logits,
+                            int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx, int width,
+                            int heads, int blocks, int bins, int out_ld, int64_t start, uint64_t seed,
+                            const int64_t* prime, int prime_len, float temperature, int top_k, float top_p,
+                            int32_t* kept, float* logp_model, float* logp_draw, vqa_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -167,6 +167,8 @@ def main():
     ap.add_argument("--top-k", type=int, default=0)
     ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--repeats", type=int, default=1)
+    ap.add_argument("--logprobs", action="store_true",
+                    help="sample mode: ask for the log-probabilities (the scored decode kernel)")
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--only", default="")
@@ -278,13 +280,17 @@ def main():
         prime = (torch.randint(0, a.bins - 1, (a.samples, a.prime_len), device=dev, generator=g)
                  if a.prime_len else None)
         opts = dict(prime=prime, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p)
+        lp = dict(return_logprobs=True) if a.logprobs else {}
+        opts.update(lp)
         m.sample(a.samples, max_length=16, x_cond=up, seed=1, temperature=a.temperature,
-                 top_k=a.top_k, top_p=a.top_p)  # warm-up (conditioner + the decode kernel that is timed)
+                 top_k=a.top_k, top_p=a.top_p, **lp)  # warm-up (conditioner + the decode kernel that is timed)
         torch.cuda.synchronize()
         els = []
         for _ in range(max(1, a.repeats)):  # one window per launch; an error raises and ends the run
             t0 = time.perf_counter()
             out_tok = m.sample(a.samples, max_length=a.sample_len, x_cond=up, seed=2, **opts)
+            if a.logprobs:
+                out_tok = out_tok[0]
             torch.cuda.synchronize()
             els.append(time.perf_counter() - t0)
         el = sorted(els)[len(els) // 2]
@@ -293,7 +299,7 @@ def main():
                           "ms_per_position": round(el / a.sample_len * 1e3, 4),
                           "ms_per_position_repeats": [round(e / a.sample_len * 1e3, 4) for e in els],
                           "prime_len": a.prime_len, "temperature": a.temperature, "top_k": a.top_k, "top_p": a.top_p,
-                          "samples": a.samples,
+                          "samples": a.samples, **({"logprobs": True} if a.logprobs else {}),
                           "positions": a.sample_len, "dtype": "fp32 (decode)",
                           "config": {"workload": "BASELINE config 5", "ctx": a.ctx, "bins": a.bins, **kw},
                           "tokens_in_range": bool(((out_tok >= 0) & (out_tok < a.bins)).all())}), flush=True)

@@ -23,7 +23,9 @@ namespace vqa {
 // (score = logit / temperature + G over the bins whose logit is >= the k-th largest of the row); the default
 // (temperature 1, top-k off) runs kFilter = false, whose arithmetic is the unfiltered decode's. kFilter = 2
 // (vqa_prior_decode_filtered with top_p < 1 or a `kept` output) is kFilter = 1 plus the nucleus threshold
-// (dec_nucleus_threshold) and the count of the bins that took part in the draw.
+// (dec_nucleus_threshold) and the count of the bins that took part in the draw. kFilter = 3
+// (vqa_prior_decode_scored with a log-probability output) is kFilter = 2 plus the two log-sums of dec_score_max /
+// dec_logprob; with both outputs NULL the host launches 0, 1 or 2 as before.
 constexpr int kDecMaxLayers = 8;
 constexpr int kDecW = 128;   // model width
 constexpr int kDecAW = 32;   // attention width (m_attn 0.25)
@@ -64,7 +66,9 @@ struct DecArgs {
   int topk;               // 0: off, else 1 <= topk < bins (kFilter only)
   float temp;             // temperature, finite and > 0 (kFilter only)
   float topp;             // nucleus mass, 0 < topp <= 1, >= 1: off (kFilter = 2 only)
-  int* kept;              // (N, steps) bins that took part in each draw, or null (kFilter = 2 only)
+  int* kept;              // (N, steps) bins that took part in each draw, or null (kFilter >= 2 only)
+  float* logp_model;      // (N, steps) log-probability of the written token under the model, or null (kFilter = 3)
+  float* logp_draw;       // (N, steps) the same under the distribution the draw was made from, or null (kFilter = 3)
 };
 
 // y[o] = b[o] + sum_k x[k] W[k][o] (W row-major (K, O), O % 4 == 0): thread (4-output chunk c, k-group kg) sums
@@ -288,6 +292,40 @@ __device__ float dec_nucleus_threshold(const float* v, int n, float thr, float t
   return fmaxf(thr, dec_unkey(prefix));
 }
 
+// The log-probability of the token written at a step (vqa_prior_decode_scored, include/vqa.h), from the row of
+// logits v[0 .. n) in LDS (n = bins: the zero-padded columns n .. ldo are never read):
+//   model: (v[tok] - m) - log sum_{e < n} exp(v[e] - m)
+//   draw:  (v[tok] - m) / T - log sum_{e: v[e] >= thr} exp((v[e] - m) / T),  -inf when v[tok] < thr
+// with m = dec_score_max: the maximum of the row (fmaxf, NaNs skipped). The top bin passes every threshold, so one m
+// serves both sums, every exponent is <= 0 and both sums are >= 1. Order: thread tid adds its bins tid, tid + 256, ...
+// in index order inside the draw loop; the 256 partial sums are combined by the tree that reduces the draw (slot tid
+// += slot tid + w, w = 128 .. 1); no atomics, so a value is bitwise the same from run to run. With T = 1 and thr =
+// -inf the division is exact and the two sums add the same numbers in the same order: draw == model bitwise.
+// Rounding, against the same fp32 logits and T in exact arithmetic, for |a| <= 32 where a = (v[tok] - m) / T:
+//   * a: one fp32 subtraction and one correctly rounded division, <= |a| 2^-23 = 3.8e-6;
+//   * a weight w = expf(a_e) is off by at most (|a_e| + 2) 2^-23 relative (its exponent as above, expf <= 2 ulp), so
+//     the sum by sum w (|a_e| + 2) 2^-23 / sum w = (E|a_e| + 2) 2^-23 with E over the softmax; E|a_e| = H - log Z
+//     <= log n <= log 2048 = 7.6: <= 1.2e-6 in the log;
+//   * the additions: at most 8 per thread and 8 tree levels, each 2^-24 relative on positive terms: <= 1e-6;
+//   * logf <= 2 ulp of a result <= log 2048: <= 1e-6; the final subtraction rounds a value below 64: <= 1.9e-6.
+// In all <= 8.9e-6 (tests/logprob_ref.py: TOL).
+__device__ float dec_score_max(const float* v, int n, float* stat) {
+  const int tid = threadIdx.x;
+  float m = -INFINITY;
+  for (int e = tid; e < n; e += 256) m = fmaxf(m, v[e]);
+  m = warp_max(m);
+  if ((tid & 63) == 0) stat[tid >> 6] = m;
+  __syncthreads();
+  return fmaxf(fmaxf(stat[0], stat[1]), fmaxf(stat[2], stat[3]));
+}
+// thread 0, after the tree: lt = the written token's logit (-inf for a token outside the vocabulary)
+__device__ __forceinline__ void dec_logprob(const DecArgs& a, size_t at, float lt, float m, float thr, float zmodel,
+                                            float zdraw) {
+  const float d = lt - m;
+  if (a.logp_model) a.logp_model[at] = d - logf(zmodel);
+  if (a.logp_draw) a.logp_draw[at] = lt >= thr ? d / a.temp - logf(zdraw) : -INFINITY;
+}
+
 template <bool kPrimed, int kFilter>
 __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
   __shared__ __attribute__((aligned(16))) float x[kDecW], x1[kDecW], hb[kDecW], r1[kDecW];
@@ -419,8 +457,12 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
       if (primed && !a.logits) {
         tok = a.prime[(size_t)n * a.prime_len + i];
         if (tid == 0) a.tokens[(size_t)n * (a.steps + 1) + i + 1] = tok;
-        if constexpr (kFilter == 2) {
+        if constexpr (kFilter >= 2) {
           if (a.kept && tid == 0) a.kept[(size_t)n * a.steps + i] = 0;
+        }
+        if constexpr (kFilter == 3) {
+          if (a.logp_model && tid == 0) a.logp_model[(size_t)n * a.steps + i] = 0.f;
+          if (a.logp_draw && tid == 0) a.logp_draw[(size_t)n * a.steps + i] = 0.f;
         }
         continue;
       }
@@ -431,21 +473,25 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
     if constexpr (kFilter != 0) {
       if (a.topk > 0) thr = dec_kth_largest(scr, a.bins, a.topk, besti, ksel);
     }
-    if constexpr (kFilter == 2) {
+    if constexpr (kFilter >= 2) {
       // bestv (the head mat-vec's scratch) is free: 256 + 2 64-bit words of it hold the mass histogram
       if (a.topp < 1.0f)
         thr = dec_nucleus_threshold(scr, a.bins, thr, a.temp, a.topp, (unsigned long long*)bestv,
                                     (unsigned long long*)bestv + 256, stat);
     }
+    float smax = 0.f, zm = 0.f, zd = 0.f;  // kFilter = 3: the row maximum, this thread's share of the two sums
+    if constexpr (kFilter == 3) smax = dec_score_max(scr, a.bins, stat);
     float bv = -INFINITY;
-    int bi = 0, nk = 0;  // nk: this thread's bins that take part (kFilter = 2)
+    int bi = 0, nk = 0;  // nk: this thread's bins that take part (kFilter >= 2)
     for (int v = tid; v < a.bins; v += 256) {
       const float lg = scr[v];
       if (a.logits) a.logits[((size_t)n * a.steps + i) * a.bins + v] = lg;
+      if constexpr (kFilter == 3) zm += expf(lg - smax);
       if constexpr (kFilter != 0) {
         if (!(lg >= thr)) continue;
       }
-      if constexpr (kFilter == 2) ++nk;
+      if constexpr (kFilter >= 2) ++nk;
+      if constexpr (kFilter == 3) zd += expf((lg - smax) / a.temp);
       const float u = prior_uniform(a.seed, (uint64_t)n, (uint64_t)i, (uint64_t)v);
       float z;
       if constexpr (kFilter != 0) z = lg / a.temp + (-logf(-logf(u)));
@@ -455,24 +501,35 @@ __global__ __launch_bounds__(256) void prior_decode_kernel(DecArgs a) {
     __syncthreads();
     bestv[tid] = bv;
     besti[tid] = bi;
-    int* nkept = (int*)scr;  // the logits are dead past the barrier above (kFilter = 2: the counts ride the tree)
-    if constexpr (kFilter == 2) nkept[tid] = nk;
+    // kFilter = 2: the logits are dead past the barrier above and the counts ride the tree in scr. kFilter = 3 still
+    // needs the written token's logit after the tree: the counts and the two sums ride in red (the attention's
+    // scratch, 1024 floats, idle from a layer's last barrier to the next step) and scr stays whole.
+    int* nkept = kFilter == 3 ? (int*)&red[0][0] : (int*)scr;
+    float* zsum = &red[0][0] + 256;  // [256] model, [256] draw
+    if constexpr (kFilter >= 2) nkept[tid] = nk;
+    if constexpr (kFilter == 3) { zsum[tid] = zm; zsum[256 + tid] = zd; }
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) {
       if (tid < w) {
         const float ov = bestv[tid + w];
         const int oi = besti[tid + w];
         if (ov > bestv[tid] || (ov == bestv[tid] && oi < besti[tid])) { bestv[tid] = ov; besti[tid] = oi; }
-        if constexpr (kFilter == 2) nkept[tid] += nkept[tid + w];
+        if constexpr (kFilter >= 2) nkept[tid] += nkept[tid + w];
+        if constexpr (kFilter == 3) { zsum[tid] += zsum[tid + w]; zsum[256 + tid] += zsum[256 + tid + w]; }
       }
       __syncthreads();
     }
-    if constexpr (kFilter == 2) {
+    if constexpr (kFilter >= 2) {
       if (a.kept && tid == 0) a.kept[(size_t)n * a.steps + i] = nkept[0];
     }
     int64_t samp = besti[0];
     if constexpr (kPrimed) {
       if (primed) samp = a.prime[(size_t)n * a.prime_len + i];
+    }
+    if constexpr (kFilter == 3) {
+      if (tid == 0)
+        dec_logprob(a, (size_t)n * a.steps + i, (samp >= 0 && samp < a.bins) ? scr[samp] : -INFINITY, smax, thr,
+                    zsum[0], zsum[256]);
     }
     if (tid == 0) a.tokens[(size_t)n * (a.steps + 1) + i + 1] = samp;
     tok = a.forced ? a.forced[(size_t)n * (a.steps + 1) + i + 1] : samp;
@@ -492,13 +549,14 @@ extern "C" size_t vqa_prior_decode_cache_bytes(int N, int depth, int ctx) {
   return ((size_t)2 * N * depth * ctx * kDecAW + (size_t)depth * kDecComposed) * sizeof(float);
 }
 
-extern "C" int vqa_prior_decode_filtered(const vqa_prior_layer* layers, int depth, const float* x_embedding,
-                                         const float* pos_embedding, const float* out_kernel, const float* out_bias,
-                                         const float* ycond, const float* xcond, const int64_t* forced, float* logits,
-                                         int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx,
-                                         int width, int heads, int blocks, int bins, int out_ld, int64_t start,
-                                         uint64_t seed, const int64_t* prime, int prime_len, float temperature,
-                                         int top_k, float top_p, int32_t* kept, vqa_stream_t stream) {
+extern "C" int vqa_prior_decode_scored(const vqa_prior_layer* layers, int depth, const float* x_embedding,
+                                       const float* pos_embedding, const float* out_kernel, const float* out_bias,
+                                       const float* ycond, const float* xcond, const int64_t* forced, float* logits,
+                                       int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx,
+                                       int width, int heads, int blocks, int bins, int out_ld, int64_t start,
+                                       uint64_t seed, const int64_t* prime, int prime_len, float temperature,
+                                       int top_k, float top_p, int32_t* kept, float* logp_model, float* logp_draw,
+                                       vqa_stream_t stream) {
   VQA_ARG(layers && x_embedding && pos_embedding && out_kernel && out_bias && tokens && cache && N > 0 && steps > 0 &&
               steps <= ctx && blocks > 0 && ctx % blocks == 0 && bins > 0 && out_ld >= bins && out_ld % 4 == 0 &&
               out_ld <= 2048,
@@ -550,20 +608,42 @@ extern "C" int vqa_prior_decode_filtered(const vqa_prior_layer* layers, int dept
   a.temp = temperature;
   a.topp = top_p;
   a.kept = kept;
+  a.logp_model = logp_model;
+  a.logp_draw = logp_draw;
   // 0: the unfiltered decode; 1: a temperature and / or top-k; 2: top-p on (top_p = 1 is off, decided here: the
-  // filter is not run, so weights that underflow drop no bin) or the kept counts asked for
-  const int filter = (top_p < 1.0f || kept) ? 2 : (a.topk > 0 || temperature != 1.0f) ? 1 : 0;
+  // filter is not run, so weights that underflow drop no bin) or the kept counts asked for; 3: a log-probability
+  // output asked for (2 plus the two log-sums; temperature 1 divides exactly and draws the unfiltered decode's tokens)
+  const int filter = (logp_model || logp_draw) ? 3
+                     : (top_p < 1.0f || kept)  ? 2
+                     : (a.topk > 0 || temperature != 1.0f) ? 1 : 0;
   hipLaunchKernelGGL(prior_decode_prep_kernel, dim3(64, depth), dim3(256), 0, (hipStream_t)stream, a);
   VQA_LAUNCHED("prior_decode_prep_kernel");
   const bool primed = prime_len > 0;
   void (*kern)(DecArgs) =
-      primed ? (filter == 2 ? prior_decode_kernel<true, 2> : filter ? prior_decode_kernel<true, 1>
-                                                                    : prior_decode_kernel<true, 0>)
-             : (filter == 2 ? prior_decode_kernel<false, 2> : filter ? prior_decode_kernel<false, 1>
-                                                                     : prior_decode_kernel<false, 0>);
+      primed ? (filter == 3   ? prior_decode_kernel<true, 3>
+                : filter == 2 ? prior_decode_kernel<true, 2>
+                : filter      ? prior_decode_kernel<true, 1>
+                              : prior_decode_kernel<true, 0>)
+             : (filter == 3   ? prior_decode_kernel<false, 3>
+                : filter == 2 ? prior_decode_kernel<false, 2>
+                : filter      ? prior_decode_kernel<false, 1>
+                              : prior_decode_kernel<false, 0>);
   hipLaunchKernelGGL(kern, dim3(N), dim3(256), 0, (hipStream_t)stream, a);
   VQA_LAUNCHED("prior_decode_kernel");
   return VQA_OK;
+}
+
+extern "C" int vqa_prior_decode_filtered(const vqa_prior_layer* layers, int depth, const float* x_embedding,
+                                         const float* pos_embedding, const float* out_kernel, const float* out_bias,
+                                         const float* ycond, const float* xcond, const int64_t* forced, float* logits,
+                                         int64_t* tokens, void* cache, size_t cache_bytes, int N, int steps, int ctx,
+                                         int width, int heads, int blocks, int bins, int out_ld, int64_t start,
+                                         uint64_t seed, const int64_t* prime, int prime_len, float temperature,
+                                         int top_k, float top_p, int32_t* kept, vqa_stream_t stream) {
+  return vqa_prior_decode_scored(layers, depth, x_embedding, pos_embedding, out_kernel, out_bias, ycond, xcond, forced,
+                                 logits, tokens, cache, cache_bytes, N, steps, ctx, width, heads, blocks, bins, out_ld,
+                                 start, seed, prime, prime_len, temperature, top_k, top_p, kept, nullptr, nullptr,
+                                 stream);
 }
 
 extern "C" int vqa_prior_decode_primed(const vqa_prior_layer* layers, int depth, const float* x_embedding,

@@ -492,14 +492,18 @@ class FMHABasedAutoregressiveModel:
 
     def sample(self, n_samples, max_length=None, x_cond=None, y_cond=None, return_attention_weights=False, seed=0,
                forced=None, return_logits=False, prime=None, temperature=1.0, top_k=0, top_p=1.0,
-               return_kept=False):
+               return_kept=False, return_logprobs=False):
         """autoregressive_fmha.py:162-240: (N, max_length + 1) int64 tokens starting with the start token, each
         next token = argmax(logits / temperature + Gumbel noise) over the top_k largest logits (0: all). One
         persistent decode launch. top_p in (0, 1] (1: off): nucleus sampling after top-k, the draw is among the
         smallest set of top bins whose softmax(logits / temperature) mass over the top-k survivors reaches top_p
         (equal logits stay in or go out together; include/vqa.h, vqa_prior_decode_filtered). return_kept: the
         (N, max_length) int32 number of bins that took part in each draw (0 at primed positions whose head is
-        skipped) is appended to what is returned.
+        skipped) is appended to what is returned. return_logprobs: the tuple (logp_model, logp_draw) of (N, max_length)
+        fp32 tensors is appended last: the log-probability of every token after the start token under the model
+        (temperature 1, every bin) and under the distribution it was drawn from (temperature, top-k and top-p applied;
+        include/vqa.h, vqa_prior_decode_scored); 0 at primed positions whose head is skipped, so a row's sum is the
+        log-likelihood of what was drawn.
         prime (N, P <= max_length) int64: the tokens after the start token that are given, not drawn (the codes a window of long-form sampling shares with the windows before it); the noise
         is keyed by the absolute step, so a prime taken from an unprimed draw of the same seed reproduces it.
         return_attention_weights (True, or layer indices): returns (tokens, weights) with the weights of
@@ -551,6 +555,7 @@ class FMHABasedAutoregressiveModel:
         logits = (torch.empty(n_samples, L, self.bins, dtype=torch.float32, device=self.device)
                   if return_logits else None)
         kept = torch.zeros(n_samples, L, dtype=torch.int32, device=self.device) if return_kept else None
+        logp = (torch.zeros(2, n_samples, L, dtype=torch.float32, device=self.device) if return_logprobs else None)
         if forced is not None:
             forced = torch.as_tensor(forced, device=self.device).long().contiguous()
             if tuple(forced.shape) != (n_samples, L + 1):
@@ -570,7 +575,8 @@ class FMHABasedAutoregressiveModel:
         V.prior_decode(layers, self.store.view(self.emb_name), self._pos().contiguous(), ow, ob, tokens,
                        self.decode_cache(n_samples), L, self.context_length, self.heads, self.blocks,
                        self.start_token, seed, ycond=yc, xcond=xc, forced=forced, logits=logits, bins=self.bins,
-                       prime=prime, temperature=temperature, top_k=top_k, top_p=top_p, kept=kept)
+                       prime=prime, temperature=temperature, top_k=top_k, top_p=top_p, kept=kept,
+                       logp_model=None if logp is None else logp[0], logp_draw=None if logp is None else logp[1])
         out = [tokens]
         if return_logits:
             out.append(logits)
@@ -580,6 +586,8 @@ class FMHABasedAutoregressiveModel:
             out.append(weights)
         if return_kept:
             out.append(kept)
+        if return_logprobs:
+            out.append((logp[0], logp[1]))
         return out[0] if len(out) == 1 else tuple(out)
 
     def sequence_loss(self, inputs, targets, x_cond=None, y_cond=None, loss_fn=None):
@@ -1029,10 +1037,10 @@ class Prior:
             t._acc.copy_(acc.to(self.device))
 
     def sample(self, n_samples, z_cond=None, y=None, return_attn_weights=False, seed=0, prime=None, temperature=1.0,
-               top_k=0, top_p=1.0):
+               top_k=0, top_p=1.0, return_logprobs=False):
         """prior.py:374-408: one window of n_ctx tokens, the start token first (as FMHABasedAutoregressiveModel.sample
         returns it; VQVAESampler drops it). y: genre labels (N,) through the LabelConditioner. prime, temperature,
-        top_k, top_p: as FMHABasedAutoregressiveModel.sample."""
+        top_k, top_p, return_logprobs: as FMHABasedAutoregressiveModel.sample."""
         if z_cond is not None and int(z_cond.shape[0]) != n_samples:
             raise ValueError(f"Batch Size not matching, Expected:{n_samples}, Getting: {int(z_cond.shape[0])}")
         y_cond = None
@@ -1045,4 +1053,4 @@ class Prior:
             y_cond = self._label_embed(y)
         return self.prior.sample(n_samples, x_cond=z_cond, y_cond=y_cond, seed=seed,
                                  return_attention_weights=return_attn_weights, prime=prime, temperature=temperature,
-                                 top_k=top_k, top_p=top_p)
+                                 top_k=top_k, top_p=top_p, return_logprobs=return_logprobs)

@@ -9,6 +9,10 @@ conditioners' up-sampling — no per-token host round trip and no per-token grap
 Long-form sampling (sample(total_length=...)): a level's codes are drawn in overlapping windows (window_starts);
 every window after the first is primed with the codes it shares with the windows before it
 (vqa_prior_decode_primed) and is still one launch.
+
+return_logprobs=True also returns, for every code, the log-probability the window that drew it gave it
+(vqa_prior_decode_scored); best_of=K draws K top-level candidates per sample and keeps the one the model finds most
+likely.
 """
 from __future__ import annotations
 
@@ -51,7 +55,7 @@ class VQVAESampler:
                                      device=device, seed=seed + l))
 
     def sample(self, n_samples, y_genre=None, seed=0, *, total_length=None, hop_lengths=None, temperature=1.0,
-               top_k=0, top_p=1.0):
+               top_k=0, top_p=1.0, return_logprobs=False, best_of=1):
         """Sampler.py:65-114: from the top level down; returns [zs_0, ..., zs_{L-1}], (n_samples, codes_l) int64
         codes without the start token.
 
@@ -59,21 +63,47 @@ class VQVAESampler:
         seed + l. Otherwise long-form sampling: total_length counts top-level codes (at least the top n_ctx) and
         level l gets total_length * hop_top / hop_l codes, drawn in windows of n_ctx_l codes that start every
         hop_lengths[l] codes (default n_ctx_l // 2; window_starts). Each window is one primed decode launch, see
-        sample_level. temperature / top_k / top_p: as FMHABasedAutoregressiveModel.sample, for every window."""
+        sample_level. temperature / top_k / top_p: as FMHABasedAutoregressiveModel.sample, for every window.
+
+        return_logprobs: returns (zs, logps) with logps[l] = (logp_model, logp_draw), two (n_samples, codes_l) fp32
+        tensors: for every code the log-probability under the model and under the distribution it was drawn from,
+        taken from the window that drew it (never from a primed position), sliced as the codes are.
+        best_of=K (an integer >= 1; 1 is the plain path): the top level draws n_samples * K candidates, sample s owning
+        the batch rows s K .. s K + K - 1 (y_genre repeated K times each, the seeds unchanged over all windows); the
+        candidate with the highest sum of logp_model over its whole top-level sequence wins, ties to the lowest row,
+        picked on the device without a read-back. The lower levels are drawn for the n_samples winners, whose
+        log-probabilities are the ones returned."""
+        if isinstance(best_of, bool) or not isinstance(best_of, (int, np.integer)) or best_of < 1:
+            raise ValueError(f"best_of {best_of!r} must be an integer >= 1")
+        K = int(best_of)
         dev = self.priors[0].device
         zs = [torch.zeros(n_samples, 0, dtype=torch.int64, device=dev) for _ in range(self.levels)]
         totals, hops = self._plan(total_length, hop_lengths)
+        logps = [None] * self.levels
         for level in reversed(range(self.levels)):
-            zs = self.sample_level(zs, level, y_genre=y_genre, seed=seed, total_length=totals[level],
-                                   hop_length=hops[level], temperature=temperature, top_k=top_k, top_p=top_p)
-        return zs
+            kw = dict(seed=seed, total_length=totals[level], hop_length=hops[level], temperature=temperature,
+                      top_k=top_k, top_p=top_p)
+            if K > 1 and level == self.levels - 1:
+                zs[level] = torch.zeros(n_samples * K, 0, dtype=torch.int64, device=dev)
+                yk = None
+                if y_genre is not None:
+                    yk = torch.as_tensor(y_genre, device=dev).long().reshape(-1).repeat_interleave(K)
+                zs, lp = self.sample_level(zs, level, y_genre=yk, return_logprobs=True, **kw)
+                rows = best_rows(lp[0], K)
+                zs[level] = zs[level][rows]
+                logps[level] = (lp[0][rows], lp[1][rows])
+            elif return_logprobs:
+                zs, logps[level] = self.sample_level(zs, level, y_genre=y_genre, return_logprobs=True, **kw)
+            else:
+                zs = self.sample_level(zs, level, y_genre=y_genre, **kw)
+        return (zs, logps) if return_logprobs else zs
 
     def sample_audio(self, n_samples, vqvae, y_genre=None, seed=0, *, level=0, chunk_codes=4096, gain=1.0,
                      **sample_kwargs):
         """sample() followed by the VQ-VAE's decoder, as the reference does after every sampling run
         (utils/tf_utils.py:196-226 generate_and_save_waves: model.decode(codes, level)): draws the codes of every
-        level (sample_kwargs: total_length, hop_lengths, temperature, top_k, top_p — the draw is sample()'s, seeds
-        included), then renders level `level`'s codes to 16-bit PCM in chunks of chunk_codes codes (VQVAE.render).
+        level (sample_kwargs: total_length, hop_lengths, temperature, top_k, top_p, best_of — the draw is sample()'s,
+        seeds included), then renders level `level`'s codes to 16-bit PCM in chunks of chunk_codes codes (VQVAE.render).
         Returns (pcm (n_samples, codes * hop) int16, clipped (n_samples,) int32, zs). The sampler and the VQ-VAE
         must have the same levels and hop lengths; codes outside the codebook — the start token of a prior whose
         bins exceed num_embeddings — raise VQVAE.render's ValueError."""
@@ -85,6 +115,8 @@ class VQVAESampler:
                              f"{[int(h) for h in self.hop_lengths]}")
         if not 0 <= int(level) < self.levels:
             raise ValueError(f"sample_audio: level {level} outside [0, {self.levels})")
+        if sample_kwargs.get("return_logprobs"):
+            raise ValueError("sample_audio returns no log-probabilities: call sample(return_logprobs=True)")
         zs = self.sample(n_samples, y_genre=y_genre, seed=seed, **sample_kwargs)
         pcm, clipped = vqvae.render(zs[level], level, chunk_codes=chunk_codes, gain=gain)
         return pcm, clipped, zs
@@ -123,7 +155,7 @@ class VQVAESampler:
         return starts
 
     def sample_level(self, zs, level, y_genre=None, seed=0, total_length=None, hop_length=None, temperature=1.0,
-                     top_k=0, top_p=1.0):
+                     top_k=0, top_p=1.0, return_logprobs=False):
         """Sampler.py:116-124 (a stub in the reference): draw level `level` given the levels above it in zs and
         return zs with that level filled. total_length: this level's codes (default one window), hop_length: the
         distance of its window starts (default n_ctx // 2).
@@ -131,7 +163,9 @@ class VQVAESampler:
         Window w at start s (window_starts) is one persistent decode launch: primed with the codes already drawn
         in [s, s + n_ctx), conditioned on get_cond(zs, s, s + n_ctx), the label embedding at its position 0 as in
         a training window, its noise seeded seed + level + levels * w (window 0 keeps the one-window seed). Only
-        the codes past the prime are appended. A failed launch raises; no later window is queued."""
+        the codes past the prime are appended. A failed launch raises; no later window is queued.
+        return_logprobs: returns (zs, (logp_model, logp_draw)), (n_samples, total) fp32 each, sliced from every
+        window's log-probabilities exactly as its codes are (Prior.sample; start token and prime removed)."""
         pr = self.priors[level]
         n_ctx = pr.context_length
         total = n_ctx if total_length is None else int(total_length)
@@ -140,14 +174,32 @@ class VQVAESampler:
         n_samples = zs[level].shape[0]
         z = zs[level][:, :0]
         zs = list(zs)
+        lpm = lpd = None
         for w, s in enumerate(starts):
             prime = z[:, s:] if z.shape[1] > s else None
             x_cond = pr.get_cond(zs, s, s + n_ctx)
             seq = pr.sample(n_samples=n_samples, z_cond=x_cond, y=y_genre, seed=seed + level + self.levels * w,
-                            prime=prime, temperature=temperature, top_k=top_k, top_p=top_p)
+                            prime=prime, temperature=temperature, top_k=top_k, top_p=top_p,
+                            return_logprobs=return_logprobs)
+            if return_logprobs:
+                # position j of a window's log-probabilities scores its token j + 1: the same slice less the start
+                seq, (wm, wd) = seq
+                wm, wd = wm[:, z.shape[1] - s:], wd[:, z.shape[1] - s:]
+                lpm = wm if lpm is None else torch.cat([lpm, wm], dim=-1)
+                lpd = wd if lpd is None else torch.cat([lpd, wd], dim=-1)
             z = torch.cat([z, seq[:, 1 + z.shape[1] - s:]], dim=-1)  # start token and prime removed
         zs[level] = z
-        return zs
+        return (zs, (lpm, lpd)) if return_logprobs else zs
+
+
+def best_rows(logp_model, K) -> torch.Tensor:
+    """(n K, codes) log-probabilities, sample s owning rows s K .. s K + K - 1 -> (n,) int64 row of every sample's
+    winner: the highest sum over the sequence, ties to the lowest row (a NaN sum ranks last). Device ops only."""
+    inf = float("inf")
+    sums = torch.nan_to_num(logp_model.sum(dim=1), nan=-inf, posinf=inf, neginf=-inf).reshape(-1, K)
+    k = torch.arange(K, device=sums.device).expand_as(sums)
+    win = torch.where(sums == sums.max(dim=1, keepdim=True).values, k, K).min(dim=1).values
+    return torch.arange(sums.shape[0], device=sums.device) * K + win
 
 
 def window_starts(total_length, n_ctx, hop_length) -> List[int]:

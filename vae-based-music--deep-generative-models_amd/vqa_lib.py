@@ -44,7 +44,7 @@ EXPORTED = [
     "vqa_seqlin_route", "vqa_seqlin_wgrad_plan", "vqa_head_bwd_plan",
     "vqa_axpy", "vqa_dropout", "vqa_scale_f32", "vqa_tf_mix", "vqa_attn_fwd", "vqa_attn_bwd", "vqa_head_wt",
     "vqa_head_fwd", "vqa_head_bwd_workspace", "vqa_head_bwd", "vqa_rowsum_workspace", "vqa_rowsum", "vqa_prior_decode_cache_bytes",
-    "vqa_prior_decode", "vqa_prior_decode_primed", "vqa_prior_decode_filtered",
+    "vqa_prior_decode", "vqa_prior_decode_primed", "vqa_prior_decode_filtered", "vqa_prior_decode_scored",
     "vqa_corpus_steps_per_epoch", "vqa_corpus_batch", "vqa_pcm_encode", "vqa_code_batch",
     "vqa_resample", "vqa_resample_route",
     "vqa_attn_weights_elems", "vqa_attn_weights",
@@ -161,6 +161,8 @@ _SIGS = {
     "vqa_prior_decode": (_I, [_P, _I] + [_P] * 10 + [_S] + [_I] * 8 + [_L, _U, _P]),
     "vqa_prior_decode_primed": (_I, [_P, _I] + [_P] * 10 + [_S] + [_I] * 8 + [_L, _U, _P, _I, _F, _I, _P]),
     "vqa_prior_decode_filtered": (_I, [_P, _I] + [_P] * 10 + [_S] + [_I] * 8 + [_L, _U, _P, _I, _F, _I, _F, _P, _P]),
+    "vqa_prior_decode_scored": (_I, [_P, _I] + [_P] * 10 + [_S] + [_I] * 8 + [_L, _U, _P, _I, _F, _I, _F, _P, _P, _P,
+                                                                                _P]),
     # device-resident corpus feed
     "vqa_corpus_steps_per_epoch": (_L, [_L, _I, _I]),
     "vqa_corpus_batch": (_I, [_P, _L, _I, _P, _P, _L, _P, _P, _P, _I, _L, _U, _P, _L, _I, _I, _I, _P]),
@@ -1093,12 +1095,14 @@ def decode_shape_error(ctx, heads, blocks) -> Optional[str]:
 
 def prior_decode(layers, emb, pos, out_w, out_b, tokens, cache, steps, ctx, heads, blocks, start, seed, ycond=None,
                  xcond=None, forced=None, logits=None, bins=None, prime=None, temperature=1.0, top_k=0, top_p=1.0,
-                 kept=None):
+                 kept=None, logp_model=None, logp_draw=None):
     """out_w (width, ld) / out_b (ld,) with ld a multiple of 4 >= bins (zero-padded columns are never sampled).
     prime (N, P) int64: the first P next-input tokens (vqa_prior_decode_primed, include/vqa.h); temperature and
     top_k as there. The defaults run the unfiltered kernel. top_p < 1 (nucleus sampling) or kept ((N, steps) int32
     output: the bins that took part in each draw) go through vqa_prior_decode_filtered; without them the call is
-    vqa_prior_decode_primed's, as before."""
+    vqa_prior_decode_primed's, as before. logp_model / logp_draw ((N, steps) fp32 outputs: the log-probability of
+    every written token under the model and under the distribution it was drawn from) go through
+    vqa_prior_decode_scored."""
     N = tokens.shape[0]
     bins = out_w.shape[1] if bins is None else int(bins)
     arr = (PriorLayerDesc * len(layers))(*layers)
@@ -1109,11 +1113,24 @@ def prior_decode(layers, emb, pos, out_w, out_b, tokens, cache, steps, ctx, head
         prime_len = int(prime.shape[1])
         if prime_len == 0:
             prime = None
+    if kept is not None and (kept.dtype != torch.int32 or tuple(kept.shape) != (N, steps)
+                             or not kept.is_contiguous()):
+        raise VQAError(f"kept must be a contiguous ({N}, {steps}) int32 tensor "
+                       f"(got {tuple(kept.shape)} {kept.dtype})")
+    if logp_model is not None or logp_draw is not None:
+        for name, t in (("logp_model", logp_model), ("logp_draw", logp_draw)):
+            if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (N, steps) or not t.is_contiguous()):
+                raise VQAError(f"{name} must be a contiguous ({N}, {steps}) float32 tensor "
+                               f"(got {tuple(t.shape)} {t.dtype})")
+        _check(lib().vqa_prior_decode_scored(arr, len(layers), ptr(emb), ptr(pos), ptr(out_w), ptr(out_b),
+                                             ptr(ycond), ptr(xcond), ptr(forced), ptr(logits), ptr(tokens),
+                                             ptr(cache), cache.numel(), N, steps, ctx, emb.shape[1], heads, blocks,
+                                             bins, out_w.shape[1], start, seed, ptr(prime), prime_len,
+                                             float(temperature), int(top_k), float(top_p), ptr(kept),
+                                             ptr(logp_model), ptr(logp_draw), stream()),
+               "vqa_prior_decode_scored")
+        return
     if float(top_p) != 1.0 or kept is not None:
-        if kept is not None and (kept.dtype != torch.int32 or tuple(kept.shape) != (N, steps)
-                                 or not kept.is_contiguous()):
-            raise VQAError(f"kept must be a contiguous ({N}, {steps}) int32 tensor "
-                           f"(got {tuple(kept.shape)} {kept.dtype})")
         _check(lib().vqa_prior_decode_filtered(arr, len(layers), ptr(emb), ptr(pos), ptr(out_w), ptr(out_b),
                                                ptr(ycond), ptr(xcond), ptr(forced), ptr(logits), ptr(tokens),
                                                ptr(cache), cache.numel(), N, steps, ctx, emb.shape[1], heads, blocks,
