@@ -10,6 +10,7 @@ import torch
 
 import vqa_lib as V
 from audio_feed import AudioCorpus, AudioFeed
+from code_feed import CodeCorpus, CodeFeed
 from oracle import reset_perm
 
 P = ctypes.c_void_p(0x1000)      # 16-byte aligned fake device pointer
@@ -88,6 +89,22 @@ def test_host_slot_rule():
     for epoch, idx in per_epoch.items():  # within an epoch the S*B*world windows are distinct
         assert len(idx) == 8 and len(set(idx)) == 8 and all(0 <= i < M for i in idx)
     assert per_epoch[0] != per_epoch[1] and per_epoch[1] != per_epoch[2]
+
+
+def test_audio_and_code_feeds_draw_the_same_slots():
+    """include/vqa.h: vqa_code_batch resolves its window exactly as vqa_corpus_batch does. The same M = 11, B = 2,
+    world = 2 and seed on both feeds: the same slots, which are the oracle's permutation of the rule's k."""
+    M, B, W, seed = 11, 2, 2, 77
+    codes = CodeCorpus.from_codes([[np.zeros(4 * M, np.int64)]], None, [8], 64, device="cpu")
+    for r, audio in enumerate(_feeds(True, seed)):
+        code = CodeFeed(codes, 0, 4, B, seed=seed, rank=r, world=W)
+        assert len(code.starts_host) == M and code.steps_per_epoch == audio.steps_per_epoch == 2
+        for step in range(6):
+            epoch, pos = divmod(step, 2)
+            ks = [(pos * W + r) * B + b for b in range(B)]
+            want = reset_perm.perm_indices(reset_perm.perm_key(seed, epoch, 0x46454544), M, ks).tolist()
+            assert audio.slots(step) == code.slots(step) == want
+            assert audio.slots(step, rank=1 - r) == code.slots(step, rank=1 - r)
 
 
 def test_host_slot_rule_sequential_without_shuffle():

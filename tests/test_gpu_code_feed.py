@@ -161,6 +161,27 @@ def test_negative_counter_folds_into_the_table(flat, shuffle):
     assert feed.step == 1
 
 
+def test_window_shorter_than_one_aligned_group(flat):
+    """n_ctx = 1, hop 1: row b of z starts PAD + b int64 in (PAD odd), so the head is the whole row (1 = T) on rows 0
+    and 2 and empty on row 1, whose code is the tail; no row holds an aligned group. Then, through the raw binding,
+    window 1 of the unshuffled step 0 is made invalid (start -1): a zero and index -1 between two exact rows."""
+    feed = CodeFeed(flat, 0, 1, 3, hop=1, seed=4)
+    guards = _guard(feed)
+    assert len(feed.starts_host) == 268 and feed.codes.data_ptr() % 16 == 8
+    for g in range(3):
+        feed.next()
+        _check(feed, guards, g, "short")
+    starts = feed.starts.clone()
+    starts[1] = -1
+    feed.codes.fill_(7)
+    V.code_batch(flat.codes[0], flat.code_lens[0], starts, None, feed.codes, index_out=feed.index, seed=0,
+                 counter=None, step=0, rank=0, world=1, shuffle=False)
+    lo = flat.codes[0][:3].cpu().numpy().astype(np.int64)
+    assert feed.index.cpu().tolist() == [0, -1, 2]
+    assert feed.codes.cpu().numpy()[:, 0].tolist() == [lo[0], 0, lo[2]] and lo[0] == flat.num_embeddings - 1
+    assert all(v.intact() for v in guards.values())
+
+
 # ---- conditioned -----------------------------------------------------------------------------------------
 def test_conditioned_rows_labels_and_index(cond):
     feed = CodeFeed(cond, 0, 20, 3, hop=8, seed=9)

@@ -97,6 +97,16 @@ def test_world2_both_ranks(corpus):
         assert sorted(np.concatenate(idx).tolist()) == list(range(10))  # the ranks share the epoch's windows
 
 
+def test_negative_counter_folds_into_the_table(corpus):
+    """S = 2: g = -3 is pos 1 of epoch -2 (divmod floors, as the kernel's fold does), ..., g = 0 pos 0 of epoch 0."""
+    feed = AudioFeed(corpus, B, seed=17)
+    feed.counter.fill_(-3)
+    for g in (-3, -2, -1, 0):
+        idx = _check(feed, feed.next(), g, "negative")
+        assert idx.min() >= 0 and idx.max() < 10
+    assert feed.step == 1
+
+
 def test_sequential_without_shuffle(corpus):
     feed = AudioFeed(corpus, B, shuffle=False)
     for g in range(3):
@@ -130,6 +140,32 @@ def test_canaries_around_x(corpus, pad):
     assert np.all(got[:pad] == np.float32(canary)) and np.all(got[pad + B * T:] == np.float32(canary))
     assert np.array_equal(got[pad:pad + B * T].reshape(B, T).view(np.uint32), want.view(np.uint32))
     assert np.array_equal(index.cpu().numpy(), idx)
+
+
+@pytest.mark.parametrize("dtype", ["i16", "f32"])
+def test_window_shorter_than_one_aligned_group(cuda, dtype):
+    """T = 2, hop 1 over one track of 12 samples (M = 11), x one float into a canary buffer: row b starts 1 + 2 b
+    floats in, so the heads up to the first 16-byte aligned output would be 3, 1, 3, 1, 3 samples and are clipped to
+    T = 2; no row holds an aligned group, and the tail is what the head leaves (0, 1, 0, 1, 0 samples). Window 2 is
+    made invalid (start -1): the zero fill at these sizes."""
+    T2 = 2
+    c = AudioCorpus.from_arrays([_tracks(dtype)[0][:12]], window=T2, hop=1, device=cuda)
+    assert len(c) == 11
+    canary = float(np.float32(-12345.678))
+    buf = torch.full((1 + B * T2 + 5,), canary, dtype=torch.float32, device=cuda)
+    x = buf[1:1 + B * T2]
+    assert x.data_ptr() % 16 == 4
+    starts = c.starts.clone()
+    starts[2] = -1
+    index = torch.full((B,), -7, dtype=torch.int64, device=cuda)
+    V.corpus_batch(c.samples, c.corpus_len, starts, None, x.view(B, T2), None, index, seed=0, counter=None, step=0,
+                   rank=0, world=1, shuffle=False)
+    want, _, _ = _ref(*_host(c), T2, B, 0, 0, 0, 1, False)
+    want[2] = 0
+    got = buf.cpu().numpy()
+    assert np.all(got[:1] == np.float32(canary)) and np.all(got[1 + B * T2:] == np.float32(canary))
+    assert np.array_equal(got[1:1 + B * T2].reshape(B, T2).view(np.uint32), want.view(np.uint32))
+    assert index.cpu().tolist() == [0, 1, -1, 3, 4]
 
 
 def test_window_outside_the_corpus_is_zeroed_not_read(corpus):

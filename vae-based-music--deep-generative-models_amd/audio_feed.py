@@ -54,7 +54,7 @@ def window_starts(track_lengths: Sequence[int], window: int, hop: Optional[int] 
     return np.concatenate(starts), np.concatenate(track)
 
 
-def _padded_len(n: int, itemsize: int) -> int:
+def padded_len(n: int, itemsize: int) -> int:
     """Samples to allocate so that n samples rounded up to 16 bytes are readable (vqa_corpus_batch's contract)."""
     per = 16 // itemsize
     return max(per, (n + per - 1) // per * per)
@@ -84,7 +84,7 @@ class AudioCorpus:
         if len(self.starts_host) and (self.starts_host.min() < 0
                                       or self.starts_host.max() + self.window > self.corpus_len):
             raise ValueError("a window of the table leaves the corpus")
-        if _padded_len(self.corpus_len, samples.element_size()) > samples.numel():
+        if padded_len(self.corpus_len, samples.element_size()) > samples.numel():
             raise ValueError("the sample tensor is not padded to 16 bytes past corpus_len")
         self.starts = torch.from_numpy(self.starts_host).to(self.device)
         self.labels = None if self.labels_host is None else torch.from_numpy(self.labels_host).to(self.device)
@@ -137,7 +137,7 @@ class AudioCorpus:
             arrs = [a.astype(np.float32) / 32768.0 if a.dtype == np.int16 else a.astype(np.float32) for a in arrs]
         lengths = np.array([len(a) for a in arrs], np.int64)
         n = int(lengths.sum())
-        host = np.zeros(_padded_len(n, np.dtype(dt).itemsize), dt)
+        host = np.zeros(padded_len(n, np.dtype(dt).itemsize), dt)
         host[:n] = np.concatenate(arrs)
         starts, track = window_starts(lengths, window, hop, max_signal_len)
         tl = None if labels is None else np.asarray(labels, np.int64)
@@ -152,7 +152,7 @@ class AudioCorpus:
         lengths = np.array([len(a) if r == sr else design(r, sr, quality).output_length(len(a))
                             for a, r in zip(arrs, rates)], np.int64)
         n = int(lengths.sum())
-        samples = torch.zeros(_padded_len(n, 4), dtype=torch.float32, device=device)
+        samples = torch.zeros(padded_len(n, 4), dtype=torch.float32, device=device)
         off = 0
         for a, r, m in zip(arrs, rates, lengths):
             m = int(m)
@@ -206,45 +206,28 @@ class AudioCorpus:
         return self.subset(train), self.subset(test)
 
 
-class AudioFeed:
-    """The device feed of one rank: every next() launches vqa_corpus_batch and then advances the device step counter
-    (vqa_counter_add), both on the current stream, so the pair can be captured in a hipGraph and replayed. Step g
-    of the run draws slot k = ((g % S)*world + rank)*B + b of epoch g // S's permutation (S = steps_per_epoch):
-    within an epoch every window is used at most once over all ranks.
+class DeviceFeed:
+    """What the device feeds of one rank share (AudioFeed here, code_feed.CodeFeed): the slot rule over a table of M
+    windows and the step counter on the device. Step g of the run draws slot k = ((g % S)*world + rank)*B + b of
+    epoch g // S's permutation (S = steps_per_epoch): within an epoch every window is used at most once over all
+    ranks. A subclass owns its batch buffers and next(), which launches the gather and then advances the counter
+    (vqa_counter_add), both on the current stream, so the pair can be captured in a hipGraph and replayed."""
 
-    x (B, T, 1) fp32, y (B,) int64 labels (when the corpus has labels) and index (B,) int64 window numbers are the
-    feed's own buffers, overwritten by each next()."""
-
-    def __init__(self, corpus: AudioCorpus, batch_size: int, seed: int = 0, shuffle: bool = True,
-                 rank: Optional[int] = None, world: Optional[int] = None, process_group=None):
-        self.corpus, self.B, self.seed, self.shuffle = corpus, int(batch_size), int(seed), bool(shuffle)
+    def __init__(self, M: int, batch_size: int, seed: int, shuffle: bool, device, rank: Optional[int],
+                 world: Optional[int], process_group):
+        self.M, self.B, self.seed, self.shuffle = int(M), int(batch_size), int(seed), bool(shuffle)
         self.rank = vqa_dp.rank(process_group) if rank is None else int(rank)
         self.world = vqa_dp.world_size(process_group) if world is None else int(world)
         if not 0 <= self.rank < self.world:
             raise ValueError(f"rank {self.rank} outside [0, {self.world})")
-        self.steps_per_epoch = V.corpus_steps_per_epoch(len(corpus), self.B, self.world)
+        self.steps_per_epoch = V.corpus_steps_per_epoch(self.M, self.B, self.world)
         if self.steps_per_epoch < 1:
-            raise ValueError(f"{len(corpus)} windows give no full step of {self.B} x {self.world} ranks")
-        dev = corpus.device
-        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.x = torch.zeros(self.B, corpus.window, 1, dtype=torch.float32, device=dev)
-        self.y = torch.zeros(self.B, dtype=torch.int64, device=dev) if corpus.labels is not None else None
-        self.index = torch.zeros(self.B, dtype=torch.int64, device=dev)
+            raise ValueError(f"{self.M} windows give no full step of {self.B} x {self.world} ranks")
+        self.counter = torch.zeros(1, dtype=torch.int64, device=device)
+        self.index = torch.zeros(self.B, dtype=torch.int64, device=device)
 
-    def next(self):
-        """Draw this rank's batch of the current step and advance the step -> x, or (x, y) with labels."""
-        c = self.corpus
-        V.corpus_batch(c.samples, c.corpus_len, c.starts, c.labels, self.x, self.y, self.index, seed=self.seed,
-                       counter=self.counter, step=0, rank=self.rank, world=self.world, shuffle=self.shuffle)
-        V.counter_add(self.counter, 1)
-        return self.x if self.y is None else (self.x, self.y)
-
-    __next__ = next
-
-    def __iter__(self):
-        """One epoch: steps_per_epoch batches from the current step on."""
-        for _ in range(self.steps_per_epoch):
-            yield self.next()
+    def __next__(self):
+        return self.next()
 
     def __len__(self) -> int:
         return self.steps_per_epoch
@@ -258,12 +241,47 @@ class AudioFeed:
         """The window numbers step `step` draws for `rank` (default: this feed's), computed on the host by the same
         rule (vqa_reset_perm_index with the feed's level)."""
         rank = self.rank if rank is None else int(rank)
-        M, S = len(self.corpus), self.steps_per_epoch
-        epoch, pos = divmod(int(step), S)
+        epoch, pos = divmod(int(step), self.steps_per_epoch)
         ks = [(pos * self.world + rank) * self.B + b for b in range(self.B)]
         if not self.shuffle:
             return ks
-        return [V.reset_perm_index(self.seed, epoch, V.FEED_PERM_LEVEL, M, k) for k in ks]
+        return [V.reset_perm_index(self.seed, epoch, V.FEED_PERM_LEVEL, self.M, k) for k in ks]
+
+    def state_dict(self):
+        return {"counter": self.step, "seed": self.seed}
+
+    def load_state_dict(self, sd):
+        """Resume: the same seed and step counter draw the same batches. A train step captured with this feed keeps
+        the seed it was captured with: after a change of seed the model runs eagerly until it is captured again."""
+        self.seed = int(sd["seed"])
+        self.counter.fill_(int(sd["counter"]))
+
+
+class AudioFeed(DeviceFeed):
+    """The VQ-VAE's device feed: every next() launches vqa_corpus_batch and advances the step (DeviceFeed).
+
+    x (B, T, 1) fp32, y (B,) int64 labels (when the corpus has labels) and index (B,) int64 window numbers are the
+    feed's own buffers, overwritten by each next()."""
+
+    def __init__(self, corpus: AudioCorpus, batch_size: int, seed: int = 0, shuffle: bool = True,
+                 rank: Optional[int] = None, world: Optional[int] = None, process_group=None):
+        super().__init__(len(corpus), batch_size, seed, shuffle, corpus.device, rank, world, process_group)
+        self.corpus = corpus
+        self.x = torch.zeros(self.B, corpus.window, 1, dtype=torch.float32, device=corpus.device)
+        self.y = torch.zeros(self.B, dtype=torch.int64, device=corpus.device) if corpus.labels is not None else None
+
+    def next(self):
+        """Draw this rank's batch of the current step and advance the step -> x, or (x, y) with labels."""
+        c = self.corpus
+        V.corpus_batch(c.samples, c.corpus_len, c.starts, c.labels, self.x, self.y, self.index, seed=self.seed,
+                       counter=self.counter, step=0, rank=self.rank, world=self.world, shuffle=self.shuffle)
+        V.counter_add(self.counter, 1)
+        return self.x if self.y is None else (self.x, self.y)
+
+    def __iter__(self):
+        """One epoch: steps_per_epoch batches from the current step on."""
+        for _ in range(self.steps_per_epoch):
+            yield self.next()
 
     def host_batch(self, step: int, rank: Optional[int] = None) -> np.ndarray:
         """The (B, T, 1) float32 batch of `step` gathered on the host from a copy of the corpus (tests, debugging)."""
@@ -275,12 +293,3 @@ class AudioFeed:
         if flat.dtype == np.int16:
             out = out / np.float32(32768.0)
         return out[:, :, None]
-
-    def state_dict(self):
-        return {"counter": self.step, "seed": self.seed}
-
-    def load_state_dict(self, sd):
-        """Resume: the same seed and step counter draw the same batches. A train step captured with this feed keeps
-        the seed it was captured with: after a change of seed the model runs eagerly until it is captured again."""
-        self.seed = int(sd["seed"])
-        self.counter.fill_(int(sd["counter"]))

@@ -17,14 +17,13 @@ audio_feed.AudioFeed.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-import vqa_dp
 import vqa_lib as V
-from audio_feed import _padded_len, window_starts
+from audio_feed import DeviceFeed, padded_len, window_starts
 from data_utils import stratified_split
 
 
@@ -69,7 +68,7 @@ class CodeCorpus:
             t = self.codes[l]
             if t.dim() != 1 or t.dtype != torch.from_numpy(np.zeros(0, code_dtype(self.num_embeddings))).dtype:
                 raise ValueError(f"level {l}: codes are a 1-D {code_dtype(self.num_embeddings).__name__} tensor")
-            if _padded_len(int(self.lengths[l].sum()), t.element_size()) > t.numel():
+            if padded_len(int(self.lengths[l].sum()), t.element_size()) > t.numel():
                 raise ValueError(f"level {l}: the code tensor is not padded to 16 bytes past its length")
         self.code_lens = [int(n.sum()) for n in self.lengths]
         self.offsets = [np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64) for n in self.lengths]
@@ -109,7 +108,7 @@ class CodeCorpus:
                 if len(a) and (int(a.min()) < 0 or int(a.max()) >= int(num_embeddings)):
                     raise ValueError(f"level {l} track {j}: a code outside [0, {int(num_embeddings)})")
             n = int(sum(len(a) for a in arrs))
-            host = np.zeros(_padded_len(n, np.dtype(dt).itemsize), dt)
+            host = np.zeros(padded_len(n, np.dtype(dt).itemsize), dt)
             host[:n] = np.concatenate(arrs).astype(dt)
             stores.append(torch.from_numpy(host).to(device))
             lengths.append([len(a) for a in arrs])
@@ -142,7 +141,7 @@ class CodeCorpus:
         stores, lengths = [], []
         for l, tracks in enumerate(per_level):
             n = sum(t.numel() for t in tracks)
-            store = torch.zeros(_padded_len(n, tracks[0].element_size()), dtype=dt, device=vqvae.device)
+            store = torch.zeros(padded_len(n, tracks[0].element_size()), dtype=dt, device=vqvae.device)
             store[:n] = torch.cat(tracks)
             stores.append(store)
             lengths.append([t.numel() for t in tracks])
@@ -191,13 +190,11 @@ class CodeCorpus:
         return cls.from_codes(tracks, labels, hops, K, device=device)
 
 
-class CodeFeed:
-    """The device feed of one rank for the prior of `level`: every next() launches vqa_code_batch and then advances
-    the device step counter (vqa_counter_add), both on the current stream, so the pair can be captured in a hipGraph
-    and replayed. The window table is built here on the host: within each track starts 0, hop, 2 hop, ... while the
-    window of n_ctx codes lies inside the track (hop defaults to n_ctx). Step g of the run draws slot
-    k = ((g % S)*world + rank)*B + b of epoch g // S's permutation — the rule, and the permutation key, of
-    audio_feed.AudioFeed.
+class CodeFeed(DeviceFeed):
+    """The device feed of one rank for the prior of `level`: every next() launches vqa_code_batch and advances the
+    step (audio_feed.DeviceFeed: the slot rule, and the permutation key, of audio_feed.AudioFeed). The window table
+    is built here on the host: within each track starts 0, hop, 2 hop, ... while the window of n_ctx codes lies
+    inside the track (hop defaults to n_ctx).
 
     conditioned (default: every level but the top): the windows of the level above come with the batch; n_ctx and
     hop, and so every start, must then be multiples of rate = hops[level + 1] / hops[level].
@@ -209,7 +206,6 @@ class CodeFeed:
                  seed: int = 0, shuffle: bool = True, conditioned: Optional[bool] = None, rank: Optional[int] = None,
                  world: Optional[int] = None, process_group=None):
         self.corpus, self.level, self.n_ctx, self.B = corpus, int(level), int(n_ctx), int(batch_size)
-        self.seed, self.shuffle = int(seed), bool(shuffle)
         if not 0 <= self.level < corpus.levels:
             raise ValueError(f"level {self.level} outside [0, {corpus.levels})")
         self.hop = self.n_ctx if hop is None else int(hop)
@@ -223,10 +219,6 @@ class CodeFeed:
         if self.n_ctx % self.rate or self.hop % self.rate:
             raise ValueError(f"a conditioned feed needs n_ctx {self.n_ctx} and hop {self.hop} to be multiples of "
                              f"rate {self.rate} (the codes of level {self.level} under one code of the level above)")
-        self.rank = vqa_dp.rank(process_group) if rank is None else int(rank)
-        self.world = vqa_dp.world_size(process_group) if world is None else int(world)
-        if not 0 <= self.rank < self.world:
-            raise ValueError(f"rank {self.rank} outside [0, {self.world})")
         # the table: window_starts over ALL tracks (offsets into the level's tensor), then the corpus' own tracks
         starts, track = window_starts(corpus.lengths[self.level], self.n_ctx, self.hop)
         keep = np.isin(track, corpus.tracks)
@@ -235,18 +227,14 @@ class CodeFeed:
         if len(self.starts_host) and (self.starts_host.min() < 0 or self.starts_host.max() + self.n_ctx
                                       > corpus.code_lens[self.level] or np.any(self.starts_host % self.rate)):
             raise ValueError("a window of the table leaves the corpus or is not a multiple of rate")
-        self.steps_per_epoch = V.corpus_steps_per_epoch(len(self.starts_host), self.B, self.world)
-        if self.steps_per_epoch < 1:
-            raise ValueError(f"{len(self.starts_host)} windows give no full step of {self.B} x {self.world} ranks")
         dev = corpus.device
+        super().__init__(len(self.starts_host), self.B, seed, shuffle, dev, rank, world, process_group)
         self.starts = torch.from_numpy(self.starts_host).to(dev)
         self.labels = None if self.labels_host is None else torch.from_numpy(self.labels_host).to(dev)
-        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
         self.codes = torch.zeros(self.B, self.n_ctx, dtype=torch.int64, device=dev)
         self.upper = (torch.zeros(self.B, self.n_ctx // self.rate, dtype=torch.int64, device=dev)
                       if self.conditioned else None)
         self.y = torch.zeros(self.B, dtype=torch.int64, device=dev) if self.labels is not None else None
-        self.index = torch.zeros(self.B, dtype=torch.int64, device=dev)
 
     def next(self):
         """Draw this rank's batch of the current step and advance the step -> (codes, upper or None, y or None)."""
@@ -259,8 +247,6 @@ class CodeFeed:
         V.counter_add(self.counter, 1)
         return self.codes, self.upper, self.y
 
-    __next__ = next
-
     def batch(self):
         """The feed's buffers as the tuple Prior.train_step / test_step take: (codes[, upper][, y])."""
         return tuple(t for t in (self.codes, self.upper, self.y) if t is not None)
@@ -270,25 +256,6 @@ class CodeFeed:
         for _ in range(self.steps_per_epoch):
             self.next()
             yield self.batch()
-
-    def __len__(self) -> int:
-        return self.steps_per_epoch
-
-    @property
-    def step(self) -> int:
-        """The device step counter (a synchronising read)."""
-        return int(self.counter.item())
-
-    def slots(self, step: int, rank: Optional[int] = None) -> List[int]:
-        """The window numbers step `step` draws for `rank` (default: this feed's), computed on the host by the same
-        rule (vqa_reset_perm_index with the feed's level)."""
-        rank = self.rank if rank is None else int(rank)
-        M, S = len(self.starts_host), self.steps_per_epoch
-        epoch, pos = divmod(int(step), S)
-        ks = [(pos * self.world + rank) * self.B + b for b in range(self.B)]
-        if not self.shuffle:
-            return ks
-        return [V.reset_perm_index(self.seed, epoch, V.FEED_PERM_LEVEL, M, k) for k in ks]
 
     def host_batch(self, step: int, rank: Optional[int] = None):
         """(codes (B, n_ctx), upper (B, n_ctx / rate) or None, y (B,) or None) int64 numpy arrays of `step`, gathered
@@ -302,12 +269,3 @@ class CodeFeed:
             up, n = c.codes[l + 1][:c.code_lens[l + 1]].cpu().numpy(), self.n_ctx // self.rate
             upper = np.stack([up[s // self.rate:s // self.rate + n] for s in self.starts_host[idx]]).astype(np.int64)
         return codes, upper, None if self.labels_host is None else self.labels_host[idx]
-
-    def state_dict(self):
-        return {"counter": self.step, "seed": self.seed}
-
-    def load_state_dict(self, sd):
-        """Resume: the same seed and step counter draw the same batches. A train step captured with this feed keeps
-        the seed it was captured with: after a change of seed the prior runs eagerly until it is captured again."""
-        self.seed = int(sd["seed"])
-        self.counter.fill_(int(sd["counter"]))

@@ -617,6 +617,25 @@ def corpus_steps_per_epoch(M: int, B: int, world: int = 1) -> int:
     return int(lib().vqa_corpus_steps_per_epoch(int(M), int(B), int(world)))
 
 
+def _feed_checks(op, int64_names, int64, stores, unit, starts, labels, labels_out, index_out, B) -> int:
+    """The checks corpus_batch and code_batch share -> M. int64: the tensors that must be int64 (int64_names in the
+    message); stores: (tensor or None, its length, its name, the length's name), each allocated up to its length
+    rounded up to 16 bytes (the kernels' memory contract)."""
+    if any(t is not None and t.dtype != torch.int64 for t in int64):
+        raise VQAError(f"{op}: {int64_names} are int64")
+    for t, n, what, length in stores:
+        if t is not None and (n * t.element_size() + 15) // 16 * 16 > t.numel() * t.element_size():
+            raise VQAError(f"{op}: the {what} tensor ({t.numel()} {unit}) does not cover {length} {n} "
+                           f"rounded up to 16 bytes")
+    M = starts.numel()
+    if labels is not None and labels.numel() != M:
+        raise VQAError(f"{op}: {labels.numel()} labels for {M} windows")
+    for t in (labels_out, index_out):
+        if t is not None and t.numel() != B:
+            raise VQAError(f"{op}: labels_out / index_out hold {B} entries")
+    return M
+
+
 def corpus_batch(corpus, corpus_len, starts, labels, x, labels_out=None, index_out=None, seed=0, counter=None,
                  step=0, rank=0, world=1, shuffle=True):
     """One step's batch of a device-resident corpus (vqa_corpus_batch, include/vqa.h): corpus is the 1-D int16 or
@@ -630,20 +649,11 @@ def corpus_batch(corpus, corpus_len, starts, labels, x, labels_out=None, index_o
         raise VQAError(f"corpus_batch: the corpus is int16 or float32 (got {corpus.dtype})")
     if x.dtype != torch.float32:
         raise VQAError("corpus_batch fills an fp32 tensor")
-    if starts.dtype != torch.int64 or any(t is not None and t.dtype != torch.int64
-                                         for t in (labels, labels_out, index_out, counter)):
-        raise VQAError("corpus_batch: starts, labels, labels_out, index_out and counter are int64")
     corpus_len = int(corpus_len)
-    if (corpus_len * corpus.element_size() + 15) // 16 * 16 > corpus.numel() * corpus.element_size():
-        raise VQAError(f"corpus_batch: the corpus tensor ({corpus.numel()} samples) does not cover corpus_len "
-                       f"{corpus_len} rounded up to 16 bytes")
-    M = starts.numel()
-    if labels is not None and labels.numel() != M:
-        raise VQAError(f"corpus_batch: {labels.numel()} labels for {M} windows")
     B, T = x.shape[0], x.numel() // x.shape[0]
-    for t in (labels_out, index_out):
-        if t is not None and t.numel() != B:
-            raise VQAError(f"corpus_batch: labels_out / index_out hold {B} entries")
+    M = _feed_checks("corpus_batch", "starts, labels, labels_out, index_out and counter",
+                     (starts, labels, labels_out, index_out, counter), [(corpus, corpus_len, "corpus", "corpus_len")],
+                     "samples", starts, labels, labels_out, index_out, B)
     _check(lib().vqa_corpus_batch(ptr(corpus), corpus_len, pcm, ptr(starts), ptr(labels), M, ptr(x), ptr(labels_out),
                                   ptr(index_out), B, T, int(seed), ptr(counter), int(step), int(rank), int(world),
                                   int(bool(shuffle)), stream()), "vqa_corpus_batch")
@@ -666,23 +676,14 @@ def code_batch(codes, codes_len, starts, labels, z, upper=None, upper_len=0, rat
         raise VQAError(f"code_batch: the codes are int16 or int32 (got {codes.dtype})")
     if upper is not None and upper.dtype != codes.dtype:
         raise VQAError(f"code_batch: upper is {upper.dtype}, codes {codes.dtype}")
-    if starts.dtype != torch.int64 or any(t is not None and t.dtype != torch.int64
-                                         for t in (z, z_upper, labels, labels_out, index_out, counter)):
-        raise VQAError("code_batch: starts, labels, z, z_upper, labels_out, index_out and counter are int64")
     codes_len, upper_len, rate = int(codes_len), int(upper_len), int(rate)
-    for t, n, what in ((codes, codes_len, "codes"), (upper, upper_len, "upper")):
-        if t is not None and (n * t.element_size() + 15) // 16 * 16 > t.numel() * t.element_size():
-            raise VQAError(f"code_batch: the {what} tensor ({t.numel()} codes) does not cover its length {n} "
-                           f"rounded up to 16 bytes")
-    M = starts.numel()
-    if labels is not None and labels.numel() != M:
-        raise VQAError(f"code_batch: {labels.numel()} labels for {M} windows")
     B, T = z.shape[0], z.numel() // z.shape[0]
+    M = _feed_checks("code_batch", "starts, labels, z, z_upper, labels_out, index_out and counter",
+                     (starts, z, z_upper, labels, labels_out, index_out, counter),
+                     [(codes, codes_len, "codes", "its length"), (upper, upper_len, "upper", "its length")], "codes",
+                     starts, labels, labels_out, index_out, B)
     if z_upper is not None and rate >= 1 and z_upper.numel() != B * (T // rate):
         raise VQAError(f"code_batch: z_upper holds {z_upper.numel()} codes, not {B} x {T // rate}")
-    for t in (labels_out, index_out):
-        if t is not None and t.numel() != B:
-            raise VQAError(f"code_batch: labels_out / index_out hold {B} entries")
     _check(lib().vqa_code_batch(ptr(codes), codes_len, ptr(upper), upper_len, rate, width, ptr(starts), ptr(labels), M,
                                 ptr(z), ptr(z_upper), ptr(labels_out), ptr(index_out), B, T, int(seed), ptr(counter),
                                 int(step), int(rank), int(world), int(bool(shuffle)), stream()), "vqa_code_batch")
