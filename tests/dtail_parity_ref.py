@@ -267,8 +267,9 @@ def uncovered(T, hop, win):
 
 def pair_walk(n_fft, cus):
     """(waves per workgroup, LDS bytes per workgroup, upper limit on resident workgroups per CU) of the frame-pair
-    kernel for n_fft: launch_pairs (Stockham, kSpecWaves = 4) / launch_pairs4 (four-step, spec4_waves<2048> = 8) of
-    csrc/vqa_spectral.hip; the limit is the smaller of 160 KiB / LDS and 32 wave slots / waves"""
+    kernel for n_fft: launch_pairs (Stockham, kSpecWaves = 4; csrc/vqa_spectral_stockham.hip) / launch_pairs4
+    (four-step, kSpec4Waves = 8; csrc/vqa_spectral_fourstep.hip); the limit is the smaller of 160 KiB / LDS and 32 wave
+    slots / waves"""
     N = n_fft
     if N == 2048:
         waves, Pn = 8, N // 64

@@ -1,4 +1,4 @@
-"""Spectral-loss kernel parity (vqa_spectral.hip) vs the CPU oracle in fp64.
+"""Spectral-loss kernel parity (vqa_spectral*.hip) vs the CPU oracle in fp64.
 
 Follows data_utils.py:25-40 (spectral / norm) and vqvae.py:309-326 (_multispectral_loss); the oracle's
 gradient is torch autograd through rfft/abs (abs'(0) = 0, as TF). Tolerances (fp32 FFT vs fp64):
@@ -6,9 +6,10 @@ magnitudes 2e-6 of the spectrum's max, loss 1e-5 relative, gradient 1e-4 of its 
 
 test_single_resolution and below use white noise (tests/dtail_parity_ref.white_signals: no bin and no sample
 dominates, so the same three bounds bind on every bin and every sample) and take one resolution at a time, so each
-of the three FFT implementations (the frame kernel, the Stockham pair kernel for 256 / 512 / 1024, the four-step pair
-kernel for 2048) is held to the bounds alone in each of its modes, at every frame geometry the layout accepts, with
-either gather kernel, down to one frame per item, and on every item of a persistent walk of three pairs per wave.
+of the two FFT implementations (the Stockham pair kernel for 256 / 512 / 1024, the four-step pair kernel for 2048) is
+held to the bounds alone in each of its modes, at every frame geometry the layout accepts, with either gather kernel,
+down to one frame per item, and on every item of a persistent walk of three pairs per wave. stft_magnitude is the pair
+kernels' self-table mode (magnitude mode with the tables evaluated in the kernel): the bits of the target buffer.
 """
 import numpy as np
 import pytest
@@ -207,11 +208,18 @@ def _single(cuda, B, T, n_fft, hop, win, tag):
     xd, rd = x.to(cuda).contiguous(), r.to(cuda).contiguous()
     F, KB = 1 + (T - win) // hop, n_fft // 2 + 1
     smax = m_ref.abs().max()
-    # magnitude mode of the pair kernel, and the frame kernel
-    e_pair = float((_target_mags(xd, B, T, n_fft, hop, win) - m_ref).abs().max() / smax)
-    fm = torch.full((B, F, KB), float("nan"), device=cuda)
+    # magnitude mode of the pair kernel, and its self-table mode (vqa_stft_magnitude; "frame" in the figures): the
+    # same table formulas and the same instructions after the prologue, so the same bits, and stores by frame
+    # (one guard frame either side of the output stays NaN)
+    tm = _target_mags(xd, B, T, n_fft, hop, win)
+    e_pair = float((tm - m_ref).abs().max() / smax)
+    guard = torch.full((B * F + 2, KB), float("nan"), device=cuda)
+    fm = guard[1:B * F + 1].view(B, F, KB)
     V.stft_magnitude(xd, fm, n_fft, hop, win)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(guard[[0, B * F + 1]]).all()), "magnitudes written outside their frames"
     e_frame = float((fm.cpu().double() - m_ref).abs().max() / smax)
+    same_bits = torch.equal(fm.cpu().view(torch.int32), tm.float().view(torch.int32))
     # gradient mode (the 8-frame gather while <= 8 frames cover a sample) and loss-only mode
     loss, item, g = _loss_grad(xd, rd, (n_fft, hop, win), 1)
     e_loss = abs(float(loss) - loss_ref) / loss_ref
@@ -222,6 +230,7 @@ def _single(cuda, B, T, n_fft, hop, win, tag):
           f"frame {e_frame:.2e} (bound {D.SPEC_MAG:.0e}) loss {e_loss:.2e} item {e_item:.2e} (bound {D.SPEC_LOSS:.0e}) "
           f"gradient {e_grad:.2e} (bound {D.SPEC_GRAD:.0e})")
     assert e_pair < D.SPEC_MAG and e_frame < D.SPEC_MAG, (e_pair, e_frame)
+    assert same_bits, "vqa_stft_magnitude differs from the target buffer's magnitudes"
     assert e_loss < D.SPEC_LOSS and e_item < D.SPEC_LOSS, (e_loss, e_item)
     assert e_grad < D.SPEC_GRAD, e_grad
     assert torch.equal(loss0.view(torch.int32), loss.view(torch.int32)) and torch.equal(item0, item)

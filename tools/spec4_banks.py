@@ -1,6 +1,7 @@
 """LDS slot conflicts of the four-step spectral kernel's bin exchange (dev tool, CPU): for N = 2048 / 1024 / 512,
 the worst number of lanes of a half wave on one 8-byte slot (32 slots of 64 banks), for the own-bin writes and the
-mirror-bin reads, under candidate paddings of the natural bin index (vqa_spectral.hip Spec4::slot uses the last).
+mirror-bin reads, under candidate paddings of the natural bin index (vqa_spectral_fourstep.hip Spec4::slot uses the
+last; the kernel itself is built for N = 2048 only).
     python tools/spec4_banks.py
 """
 import itertools

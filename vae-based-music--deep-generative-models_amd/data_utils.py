@@ -4,8 +4,8 @@ data_utils.py:19-22  STFT_ARGS (n_fft, hop_length, window_size) per resolution
 data_utils.py:25-30  spectral = |tf.signal.stft(x, frame_length=win, frame_step=hop, fft_length=n_fft)|
 data_utils.py:33-40  norm = tf.norm(x, 'fro', axis=[-2, -1])
 vqvae.py:309-326     _multispectral_loss = mean_res ||S_x - S_r||_F / ||S_x||_F
-The STFT, the loss and its gradient run in libvqa's spectral kernels (csrc/vqa_spectral.hip: in-LDS radix-4
-FFTs with TF framing — no centering, frame t = x[t*hop : t*hop+win] times a periodic Hann window, rfft
+The STFT, the loss and its gradient run in libvqa's spectral kernels (csrc/vqa_spectral*.hip: one wave per frame
+pair, a Stockham or four-step FFT in registers and LDS, with TF framing — no centering, frame t = x[t*hop : t*hop+win] times a periodic Hann window, rfft
 zero-padded at the end to n_fft).
 
 data_utils.py:43-238  load_audio, splitsongs, split_convert, read_data, generate_genre_samples: a folder of
