@@ -328,6 +328,32 @@ int vqa_adam_keras_clipped(float* w, const float* g, float* m, float* v, int64_t
                            const int64_t* seg_start, const int32_t* block_seg, int nseg, int modes, float clipvalue,
                            float clipnorm, float global_clipnorm, const float* seg_norm, const float* stats,
                            vqa_stream_t stream);
+/* ---- weight averaging: an exponential moving average of the parameters in the Adam launch itself
+ *      (tensorflow_addons' MovingAverage / tf.train.ExponentialMovingAverage; TF's assign_moving_average without
+ *      zero-debias). The rule, for one step with t = *step (the count before this step's increment, what
+ *      vqa_lr_schedule reads) and w_new the weight the Adam update leaves:
+ *   d    = 0                                                 if t < start_step
+ *        = min(average_decay, (1 + n) / (10 + n)), n = t - start_step, in fp32      if dynamic
+ *        = average_decay                                     otherwise
+ *   ema  = w_new                                             if d == 0 (a copy: the average is the weights bitwise)
+ *        = ema - (ema - w_new) * (1 - d)                     otherwise, fp32, 1 - d formed once per launch
+ * over all n elements. One pass: w, g, m, v and ema are read once, w, m, v and ema written once; w, m and v come
+ * out bitwise as from the entry point without the average. average_decay must be finite and in [0, 1),
+ * start_step >= 0, dynamic 0 or 1; ema must not overlap w. */
+/* vqa_adam_keras plus the average. 16-byte accesses when w, g, m, v and ema are all 16-byte aligned. */
+int vqa_adam_keras_ema(float* w, const float* g, float* m, float* v, int64_t n, const int64_t* step, float lr,
+                       const float* lr_dev, float beta1, float beta2, float eps, float grad_scale, float* ema,
+                       float average_decay, int64_t start_step, int dynamic, vqa_stream_t stream);
+/* vqa_adam_keras_clipped plus the average; ema must be 16-byte aligned like w, g, m and v. */
+int vqa_adam_keras_clipped_ema(float* w, const float* g, float* m, float* v, int64_t n, const int64_t* step, float lr,
+                               const float* lr_dev, float beta1, float beta2, float eps, float grad_scale,
+                               const int64_t* seg_start, const int32_t* block_seg, int nseg, int modes,
+                               float clipvalue, float clipnorm, float global_clipnorm, const float* seg_norm,
+                               const float* stats, float* ema, float average_decay, int64_t start_step, int dynamic,
+                               vqa_stream_t stream);
+/* a[i] <-> b[i] for i in [0, n): exact, in place, no temporary (tfa's swap_weights adds and subtracts, which is
+ * not exact). a and b must not be the same buffer or overlap. */
+int vqa_swap_f32(float* a, float* b, int64_t n, vqa_stream_t stream);
 /* keras LearningRateSchedule at the optimizer's device step counter (OptimizerV2._decayed_lr: schedule(float(
  * iterations)), before the step's increment): *lr = f(*step), so a captured train step replays with the right rate.
  * kind 0: p0. kind 1, CustomSchedule (src/transformer/multi_head_attention.py:82-101): p0 = rsqrt(d_model),

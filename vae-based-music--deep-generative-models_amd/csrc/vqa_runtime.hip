@@ -6,6 +6,8 @@
 //                    one launch over the flat fp32 parameter buffer of all levels.
 //   vqa_grad_norm / vqa_adam_keras_clipped : OptimizerV2's clipvalue / clipnorm / global_clipnorm on the stream
 //                    (a deterministic norm pass, then the same update on the clipped gradient).
+//   vqa_adam_keras_ema / vqa_adam_keras_clipped_ema : the same updates with an exponential moving average of the
+//                    weights kept in the same pass; vqa_swap_f32 exchanges the weights and their average.
 #include "vqa_launch.h"
 #include <stdarg.h>
 #include <stdio.h>
@@ -129,22 +131,122 @@ __global__ __launch_bounds__(256) void mse_reduce_kernel(const float* ws, int n,
 
 // TF ApplyAdam (training_ops.cc, non-nesterov): alpha = lr*sqrt(1-b2^t)/(1-b1^t);
 // m += (g - m)*(1-b1); v += (g*g - v)*(1-b2); var -= (m*alpha)/(sqrt(v) + eps).
+// The step's scalars and the update of one element on the (scaled, clipped) gradient u: the one statement of the
+// arithmetic, shared by every Adam kernel below, so w, m and v come out bitwise the same from each of them.
+struct AdamStep {
+  float alpha, omb1, omb2, eps;
+  __device__ __forceinline__ AdamStep(const int64_t* step, float lr0, const float* lr_dev, float b1, float b2,
+                                      float eps_)
+      : eps(eps_) {
+    const float lr = lr_dev ? lr_dev[0] : lr0;  // a LearningRateSchedule's value at this step (vqa_lr_schedule)
+    const float t = (float)(step[0] + 1);
+    const float b1p = powf(b1, t), b2p = powf(b2, t);
+    alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
+    omb1 = 1.f - b1;
+    omb2 = 1.f - b2;
+  }
+  __device__ __forceinline__ void moments(float u, float& mi, float& vi) const {
+    mi = mi + (u - mi) * omb1;
+    vi = vi + (u * u - vi) * omb2;
+  }
+  // the new weight from the old one and the moments that moments() left
+  __device__ __forceinline__ float weight(float wi, float mi, float vi) const {
+    return wi - (mi * alpha) / (sqrtf(vi) + eps);
+  }
+};
+
+// The moving average of the weights for one launch (tfa MovingAverage's rule, TF's assign_moving_average without
+// zero-debias), keyed by the same device step count t = *step as the learning-rate schedule:
+//   d = 0 below start_step; min(decay, (1 + n) / (10 + n)), n = t - start_step, when dynamic; decay otherwise
+//   a = w_new where d == 0 (a copy: the average is the weights bitwise), else a - (a - w_new) * (1 - d)
+// d and 1 - d are formed once, the same for every element and on every rank.
+struct EmaStep {
+  float omd;
+  bool copy;
+  __device__ __forceinline__ EmaStep(const int64_t* step, float decay, long long start, int dynamic) {
+    const long long t = step[0];
+    float d = decay;
+    if (t < start) {
+      d = 0.f;
+    } else if (dynamic) {
+      const float n = (float)(t - start);
+      d = fminf(decay, (1.f + n) / (10.f + n));
+    }
+    copy = d == 0.f;
+    omd = 1.f - d;
+  }
+  __device__ __forceinline__ float update(float a, float w_new) const {
+    return copy ? w_new : a - (a - w_new) * omd;
+  }
+};
+
 __global__ __launch_bounds__(256) void adam_kernel(float* w, const float* g, float* m, float* v, long long n,
                                                   const int64_t* step, float lr0, const float* lr_dev, float b1,
                                                   float b2, float eps, float gs) {
-  const float lr = lr_dev ? lr_dev[0] : lr0;  // a LearningRateSchedule's value at this step (vqa_lr_schedule)
-  const float t = (float)(step[0] + 1);
-  const float b1p = powf(b1, t), b2p = powf(b2, t);
-  const float alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
-  const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+  const AdamStep ad(step, lr0, lr_dev, b1, b2, eps);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     const float gi = g[i] * gs;
     float mi = m[i], vi = v[i];
-    mi = mi + (gi - mi) * omb1;
-    vi = vi + (gi * gi - vi) * omb2;
+    ad.moments(gi, mi, vi);
     m[i] = mi;
     v[i] = vi;
-    w[i] = w[i] - (mi * alpha) / (sqrtf(vi) + eps);
+    w[i] = ad.weight(w[i], mi, vi);
+  }
+}
+
+// adam_kernel with the weights' moving average in the same pass: every buffer read once, w, m, v and ema written
+// once. The first n4 groups of four go as 16-byte accesses (n4 = n / 4 when all five buffers are 16-byte aligned,
+// else 0), the elements from 4 * n4 on one by one; both loops stride over the grid.
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* w, const float* g, float* m, float* v, float* ema,
+                                                      long long n, long long n4, const int64_t* step, float lr0,
+                                                      const float* lr_dev, float b1, float b2, float eps, float gs,
+                                                      float decay, long long start, int dynamic) {
+  const AdamStep ad(step, lr0, lr_dev, b1, b2, eps);
+  const EmaStep av(step, decay, start, dynamic);
+  const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = first; i < n4; i += stride) {
+    const f32x4 gq = ((const f32x4*)g)[i];
+    f32x4 mq = ((const f32x4*)m)[i], vq = ((const f32x4*)v)[i], wq = ((const f32x4*)w)[i], aq = ((const f32x4*)ema)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float mi = mq[k], vi = vq[k];
+      ad.moments(gq[k] * gs, mi, vi);
+      mq[k] = mi;
+      vq[k] = vi;
+      wq[k] = ad.weight(wq[k], mi, vi);
+      aq[k] = av.update(aq[k], wq[k]);
+    }
+    ((f32x4*)m)[i] = mq;
+    ((f32x4*)v)[i] = vq;
+    ((f32x4*)w)[i] = wq;
+    ((f32x4*)ema)[i] = aq;
+  }
+  for (long long i = 4 * n4 + first; i < n; i += stride) {
+    float mi = m[i], vi = v[i];
+    ad.moments(g[i] * gs, mi, vi);
+    const float wi = ad.weight(w[i], mi, vi), ai = av.update(ema[i], wi);
+    m[i] = mi;
+    v[i] = vi;
+    w[i] = wi;
+    ema[i] = ai;
+  }
+}
+
+// a <-> b, element by element: exact, no temporary buffer. 16-byte accesses for the first n4 groups of four
+// (n4 = n / 4 when both buffers are 16-byte aligned, else 0), then one by one.
+__global__ __launch_bounds__(256) void swap_kernel(float* a, float* b, long long n, long long n4) {
+  const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = first; i < n4; i += stride) {
+    const f32x4 x = ((const f32x4*)a)[i], y = ((const f32x4*)b)[i];
+    ((f32x4*)a)[i] = y;
+    ((f32x4*)b)[i] = x;
+  }
+  for (long long i = 4 * n4 + first; i < n; i += stride) {
+    const float x = a[i], y = b[i];
+    a[i] = y;
+    b[i] = x;
   }
 }
 
@@ -321,16 +423,13 @@ __global__ __launch_bounds__(256) void grad_norm_stats_kernel(const float* seg_r
 // norm kept), then global_clipnorm (u * stats[2]) — OptimizerV2._transform_gradients' order. g is only read. A
 // float4 never straddles two variables (offsets are multiples of 4), so a thread finds its variable once per
 // float4, walking forward from the block's first one.
-__global__ __launch_bounds__(256) void adam_clip_kernel(float* w, const float* g, float* m, float* v, long long n,
-                                                       const int64_t* step, float lr0, const float* lr_dev, float b1,
-                                                       float b2, float eps, float gs, const int64_t* seg_start,
-                                                       const int* block_seg, int nseg, int modes, float cv, float cn,
-                                                       const float* seg_norm, const float* stats) {
-  const float lr = lr_dev ? lr_dev[0] : lr0;
-  const float t = (float)(step[0] + 1);
-  const float b1p = powf(b1, t), b2p = powf(b2, t);
-  const float alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
-  const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+// EMA: the weights' moving average (EmaStep) goes with them, ema read and written like w.
+template <bool EMA>
+__device__ __forceinline__ void adam_clip_body(float* w, const float* g, float* m, float* v, long long n,
+                                               const AdamStep& ad, float gs, const int64_t* seg_start,
+                                               const int* block_seg, int nseg, int modes, float cv, float cn,
+                                               const float* seg_norm, const float* stats, float* ema,
+                                               const EmaStep* av) {
   const float gscale = (modes & VQA_CLIP_GLOBAL_NORM) ? stats[2] : 1.f;
   const long long b0 = (long long)blockIdx.x * kClipBlock;
   int s = 0;
@@ -353,12 +452,13 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* w, const float* g
       den = nm < cn ? cn : nm;  // max(norm, c); a NaN norm compares false and stays
     }
     const int cnt = n - p >= 4 ? 4 : (int)(n - p);
-    f32x4 gq, mq, vq, wq;
+    f32x4 gq, mq, vq, wq, aq = {0.f, 0.f, 0.f, 0.f};
     if (cnt == 4) {
       gq = *(const f32x4*)(g + p);
       mq = *(const f32x4*)(m + p);
       vq = *(const f32x4*)(v + p);
       wq = *(const f32x4*)(w + p);
+      if (EMA) aq = *(const f32x4*)(ema + p);
     } else {
       for (int k = 0; k < 4; ++k) {
         const bool in = k < cnt;
@@ -366,6 +466,7 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* w, const float* g
         mq[k] = in ? m[p + k] : 0.f;
         vq[k] = in ? v[p + k] : 0.f;
         wq[k] = in ? w[p + k] : 0.f;
+        if (EMA) aq[k] = in ? ema[p + k] : 0.f;
       }
     }
 #pragma unroll
@@ -375,24 +476,48 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* w, const float* g
       if (modes & VQA_CLIP_NORM) u = (u * cn) / den;
       if (modes & VQA_CLIP_GLOBAL_NORM) u = u * gscale;
       float mi = mq[k], vi = vq[k];
-      mi = mi + (u - mi) * omb1;
-      vi = vi + (u * u - vi) * omb2;
+      ad.moments(u, mi, vi);
       mq[k] = mi;
       vq[k] = vi;
-      wq[k] = wq[k] - (mi * alpha) / (sqrtf(vi) + eps);
+      wq[k] = ad.weight(wq[k], mi, vi);
+      if (EMA) aq[k] = av->update(aq[k], wq[k]);
     }
     if (cnt == 4) {
       *(f32x4*)(m + p) = mq;
       *(f32x4*)(v + p) = vq;
       *(f32x4*)(w + p) = wq;
+      if (EMA) *(f32x4*)(ema + p) = aq;
     } else {
       for (int k = 0; k < cnt; ++k) {
         m[p + k] = mq[k];
         v[p + k] = vq[k];
         w[p + k] = wq[k];
+        if (EMA) ema[p + k] = aq[k];
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void adam_clip_kernel(float* w, const float* g, float* m, float* v, long long n,
+                                                       const int64_t* step, float lr0, const float* lr_dev, float b1,
+                                                       float b2, float eps, float gs, const int64_t* seg_start,
+                                                       const int* block_seg, int nseg, int modes, float cv, float cn,
+                                                       const float* seg_norm, const float* stats) {
+  const AdamStep ad(step, lr0, lr_dev, b1, b2, eps);
+  adam_clip_body<false>(w, g, m, v, n, ad, gs, seg_start, block_seg, nseg, modes, cv, cn, seg_norm, stats, nullptr,
+                        nullptr);
+}
+
+__global__ __launch_bounds__(256) void adam_clip_ema_kernel(float* w, const float* g, float* m, float* v, float* ema,
+                                                           long long n, const int64_t* step, float lr0,
+                                                           const float* lr_dev, float b1, float b2, float eps,
+                                                           float gs, const int64_t* seg_start, const int* block_seg,
+                                                           int nseg, int modes, float cv, float cn,
+                                                           const float* seg_norm, const float* stats, float decay,
+                                                           long long start, int dynamic) {
+  const AdamStep ad(step, lr0, lr_dev, b1, b2, eps);
+  const EmaStep av(step, decay, start, dynamic);
+  adam_clip_body<true>(w, g, m, v, n, ad, gs, seg_start, block_seg, nseg, modes, cv, cn, seg_norm, stats, ema, &av);
 }
 
 // keras LearningRateSchedule evaluated on the device at the optimizer's step counter (OptimizerV2._decayed_lr
@@ -527,6 +652,52 @@ extern "C" int vqa_adam_keras(float* w, const float* g, float* m, float* v, int6
   return VQA_OK;
 }
 
+// ---- the weights' moving average: argument checks shared by the two averaging updates
+static bool overlap(const float* a, const float* b, int64_t n) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+  return x < y ? y - x < bytes : x - y < bytes;
+}
+
+static int ema_check(const char* what, const float* w, const float* ema, int64_t n, float average_decay,
+                     int64_t start_step, int dynamic) {
+  VQA_ARG(n > 0, "%s: n must be > 0 (got %lld)", what, (long long)n);
+  VQA_ARG(ema, "%s: null average", what);
+  VQA_ARG(!w || !overlap(w, ema, n), "%s: the average must not alias the weights", what);
+  VQA_ARG(std::isfinite(average_decay) && average_decay >= 0.f && average_decay < 1.f,
+          "%s: average_decay must be finite and in [0, 1) (got %g)", what, (double)average_decay);
+  VQA_ARG(start_step >= 0, "%s: start_step must be >= 0 (got %lld)", what, (long long)start_step);
+  VQA_ARG(dynamic == 0 || dynamic == 1, "%s: dynamic must be 0 or 1 (got %d)", what, dynamic);
+  return VQA_OK;
+}
+
+extern "C" int vqa_adam_keras_ema(float* w, const float* g, float* m, float* v, int64_t n, const int64_t* step,
+                                  float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                                  float grad_scale, float* ema, float average_decay, int64_t start_step, int dynamic,
+                                  vqa_stream_t stream) {
+  const int rc = ema_check("adam_ema", w, ema, n, average_decay, start_step, dynamic);
+  if (rc != VQA_OK) return rc;
+  VQA_ARG(w && g && m && v && step, "adam_ema: null pointer");
+  const bool wide = ((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) % 16 == 0;
+  const long long n4 = wide ? n / 4 : 0;
+  hipLaunchKernelGGL(adam_ema_kernel, dim3(blocks_for(wide ? n4 : n, 4096)), dim3(256), 0, (hipStream_t)stream, w,
+                     g, m, v, ema, (long long)n, n4, step, lr, lr_dev, beta1, beta2, eps, grad_scale, average_decay,
+                     (long long)start_step, dynamic);
+  VQA_LAUNCHED("adam_ema_kernel");
+  return VQA_OK;
+}
+
+extern "C" int vqa_swap_f32(float* a, float* b, int64_t n, vqa_stream_t stream) {
+  VQA_ARG(n > 0, "swap: n must be > 0 (got %lld)", (long long)n);
+  VQA_ARG(a && b, "swap: null pointer");
+  VQA_ARG(a != b && !overlap(a, b, n), "swap: the two buffers must not be the same or overlap");
+  const bool wide = ((uintptr_t)a | (uintptr_t)b) % 16 == 0;
+  const long long n4 = wide ? n / 4 : 0;
+  hipLaunchKernelGGL(swap_kernel, dim3(blocks_for(wide ? n4 : n, 4096)), dim3(256), 0, (hipStream_t)stream, a, b,
+                     (long long)n, n4);
+  VQA_LAUNCHED("swap_kernel");
+  return VQA_OK;
+}
+
 // ---- gradient clipping: argument checks shared by the norm pass and the clipped update
 static long long clip_blocks(int64_t n) { return (n + kClipBlock - 1) / kClipBlock; }
 
@@ -599,6 +770,26 @@ extern "C" int vqa_adam_keras_clipped(float* w, const float* g, float* m, float*
                      (long long)n, step, lr, lr_dev, beta1, beta2, eps, grad_scale, seg_start, block_seg, nseg, modes,
                      clipvalue, clipnorm, seg_norm, stats);
   VQA_LAUNCHED("adam_clip_kernel");
+  return VQA_OK;
+}
+
+extern "C" int vqa_adam_keras_clipped_ema(float* w, const float* g, float* m, float* v, int64_t n, const int64_t* step,
+                                          float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                                          float grad_scale, const int64_t* seg_start, const int32_t* block_seg,
+                                          int nseg, int modes, float clipvalue, float clipnorm, float global_clipnorm,
+                                          const float* seg_norm, const float* stats, float* ema, float average_decay,
+                                          int64_t start_step, int dynamic, vqa_stream_t stream) {
+  int rc = clip_check("adam_clipped_ema", n, seg_start, block_seg, nseg, modes, clipvalue, clipnorm, global_clipnorm);
+  if (rc != VQA_OK) return rc;
+  rc = ema_check("adam_clipped_ema", w, ema, n, average_decay, start_step, dynamic);
+  if (rc != VQA_OK) return rc;
+  VQA_ARG(w && g && m && v && step && seg_norm && stats, "adam_clipped_ema: null pointer");
+  VQA_ARG(((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) % 16 == 0,
+          "adam_clipped_ema: w, g, m, v and ema must be 16-byte aligned");
+  hipLaunchKernelGGL(adam_clip_ema_kernel, dim3((int)clip_blocks(n)), dim3(256), 0, (hipStream_t)stream, w, g, m, v,
+                     ema, (long long)n, step, lr, lr_dev, beta1, beta2, eps, grad_scale, seg_start, block_seg, nseg,
+                     modes, clipvalue, clipnorm, seg_norm, stats, average_decay, (long long)start_step, dynamic);
+  VQA_LAUNCHED("adam_clip_ema_kernel");
   return VQA_OK;
 }
 

@@ -38,7 +38,8 @@ from vqa_layers import CKPT_VERSION, ParamStore, checkpoint_layout
 from vqa_metrics import Mean
 from vqa_module import keras_evaluate, keras_fit_feed
 from vqa_optim import Adam
-from vqa_train import CapturedStep, adam_from_checkpoint, adam_state, set_adam_state
+from vqa_train import (CapturedStep, adam_from_checkpoint, adam_state, averaged_weights, refuse_averaged,
+                       set_adam_state)
 
 
 def create_look_ahead_mask(q_len, k_len):
@@ -686,6 +687,19 @@ class Prior:
         self.teacher_seed = 3
         self._step = 0
         self._captured: Optional[CapturedStep] = None
+        self._in_average = False  # inside averaged_weights()
+
+    def averaged_weights(self):
+        """`with prior.averaged_weights():` runs the body on the moving average of the weights that an optimizer built
+        with average_decay keeps (vqa_optim.Adam): evaluate, test_step, __call__ (return_attention_weights included),
+        sample and get_weights see the averaged weights (every weight image is made per call from the store); on
+        exit, also by an exception, the trained weights are back bitwise. train_step, fit, capture_train_step,
+        compile, save, load and entering again raise RuntimeError inside, before anything is launched. ValueError
+        when the optimizer keeps no average."""
+        return averaged_weights(self, self.prior.store)
+
+    def get_weights(self) -> Dict[str, np.ndarray]:
+        return self.prior.store.values()
 
     # None or the captured (g1, g2), g2 None in the one-graph form; the CodeFeed the step draws from (None: a copy-in)
     _graph = property(lambda self: self._captured and self._captured.graphs)
@@ -700,6 +714,7 @@ class Prior:
         vqa_optim.Adam whose learning_rate is a float or a LearningRateSchedule such as
         schedules.CustomSchedule(d_model) (src/transformer/multi_head_attention.py:82-101), evaluated on the
         device each step. A captured step is dropped (it holds the previous optimizer's buffers)."""
+        refuse_averaged(self, "compile")
         self.optimizer = optimizer or Adam()
         self.optimizer.build(self.prior.store)
         self._captured = None
@@ -874,6 +889,7 @@ class Prior:
 
     def train_step(self, x, teacher_force_rate=0.2, tf_mask=None):
         """prior.py:241-335. tf_mask (N, T) bool overrides the random teacher-forcing draw (parity tests)."""
+        refuse_averaged(self, "train_step")
         # the captured graph bakes in its teacher-forcing rate: another rate (e.g. a schedule) runs eagerly
         replayable = (self._captured is not None and tf_mask is None
                       and float(teacher_force_rate) == self._graph_rate)
@@ -980,6 +996,7 @@ class Prior:
         codes_example may be a code_feed.CodeFeed: its gather launch and counter increment are then recorded at the
         head of the first graph and the graph's inputs are the feed's own buffers (no copy); the warm-up steps are
         real steps on the feed's next batches, and a later train_step(feed) with this feed replays."""
+        refuse_averaged(self, "capture_train_step")
         feed = codes_example if isinstance(codes_example, CodeFeed) else None
         self._captured = None
         if feed is not None:
@@ -1002,6 +1019,7 @@ class Prior:
         """Minimal keras fit over a code_feed.CodeFeed: the trackers reset per epoch (keras semantics), an epoch is
         the feed's steps_per_epoch steps (graph replays once the step is captured with that feed); batch size,
         shuffling and seed are the feed's. Returns the history of epoch-end results."""
+        refuse_averaged(self, "fit")
         if not isinstance(x, CodeFeed):
             raise ValueError("Prior.fit trains from a code_feed.CodeFeed")
         self._check_feed(x)
@@ -1013,7 +1031,8 @@ class Prior:
         VQ-VAE, src/callback/monitors.py): tensors, ints and strings only — `torch.load(path, weights_only=True)`
         reads it. Weights (the ConditionerNet's and the genre table's included), Adam moments and step (the step
         also drives teacher forcing and dropout), and the loss / accuracy trackers: resuming reproduces the
-        uninterrupted run bit for bit."""
+        uninterrupted run bit for bit. An optimizer that averages the weights adds the average (adam_ema)."""
+        refuse_averaged(self, "save")
         st = self.prior.store
         out = {"format": f"vqa-prior/{CKPT_VERSION}", "param_names": [n for n, _, _ in st.specs],
                "layout": st.layout_record(),
@@ -1026,12 +1045,15 @@ class Prior:
 
     def load(self, path: str):
         """Restore a `save` checkpoint (loaded weights-only: nothing in the file is executed); format /2 is
-        copied tensor by tensor through its recorded layout, /1 in the layout its length identifies."""
+        copied tensor by tensor through its recorded layout, /1 in the layout its length identifies. A file without
+        a weight average loaded into an averaging optimizer starts the average from the loaded weights; a file's
+        average is ignored by an optimizer that keeps none."""
+        refuse_averaged(self, "load")
         ck = torch.load(path, map_location="cpu", weights_only=True)
         st = self.prior.store
         lay = checkpoint_layout(ck, st, "prior", path)
         st.flat.copy_(st.from_layout(ck["weights"], lay, path).to(self.device))
-        set_adam_state(self.optimizer, adam_from_checkpoint(ck, st, lay, path), self.device)
+        set_adam_state(self.optimizer, adam_from_checkpoint(ck, st, lay, path), self.device, st)
         self._step = int(ck["step"])
         for t, acc in zip(self.metrics, ck["trackers"]):
             t._acc.copy_(acc.to(self.device))

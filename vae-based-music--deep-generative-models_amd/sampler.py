@@ -13,9 +13,13 @@ every window after the first is primed with the codes it shares with the windows
 return_logprobs=True also returns, for every code, the log-probability the window that drew it gave it
 (vqa_prior_decode_scored); best_of=K draws K top-level candidates per sample and keeps the one the model finds most
 likely.
+
+averaged=True draws every level from the moving average of its prior's weights (Prior.averaged_weights; the
+optimizer's average_decay), and sample_audio also renders through the VQ-VAE's averaged weights.
 """
 from __future__ import annotations
 
+from contextlib import nullcontext
 from typing import List, Optional
 
 import numpy as np
@@ -55,7 +59,7 @@ class VQVAESampler:
                                      device=device, seed=seed + l))
 
     def sample(self, n_samples, y_genre=None, seed=0, *, total_length=None, hop_lengths=None, temperature=1.0,
-               top_k=0, top_p=1.0, return_logprobs=False, best_of=1):
+               top_k=0, top_p=1.0, return_logprobs=False, best_of=1, averaged=False):
         """Sampler.py:65-114: from the top level down; returns [zs_0, ..., zs_{L-1}], (n_samples, codes_l) int64
         codes without the start token.
 
@@ -72,7 +76,11 @@ class VQVAESampler:
         the batch rows s K .. s K + K - 1 (y_genre repeated K times each, the seeds unchanged over all windows); the
         candidate with the highest sum of logp_model over its whole top-level sequence wins, ties to the lowest row,
         picked on the device without a read-back. The lower levels are drawn for the n_samples winners, whose
-        log-probabilities are the ones returned."""
+        log-probabilities are the ones returned.
+        averaged=True: every level is drawn under its prior's averaged_weights(); a prior whose optimizer keeps no
+        average is a ValueError before anything is drawn."""
+        if averaged:
+            self._check_averaged(self.priors)
         if isinstance(best_of, bool) or not isinstance(best_of, (int, np.integer)) or best_of < 1:
             raise ValueError(f"best_of {best_of!r} must be an integer >= 1")
         K = int(best_of)
@@ -82,7 +90,7 @@ class VQVAESampler:
         logps = [None] * self.levels
         for level in reversed(range(self.levels)):
             kw = dict(seed=seed, total_length=totals[level], hop_length=hops[level], temperature=temperature,
-                      top_k=top_k, top_p=top_p)
+                      top_k=top_k, top_p=top_p, averaged=averaged)
             if K > 1 and level == self.levels - 1:
                 zs[level] = torch.zeros(n_samples * K, 0, dtype=torch.int64, device=dev)
                 yk = None
@@ -99,14 +107,16 @@ class VQVAESampler:
         return (zs, logps) if return_logprobs else zs
 
     def sample_audio(self, n_samples, vqvae, y_genre=None, seed=0, *, level=0, chunk_codes=4096, gain=1.0,
-                     **sample_kwargs):
+                     averaged=False, **sample_kwargs):
         """sample() followed by the VQ-VAE's decoder, as the reference does after every sampling run
         (utils/tf_utils.py:196-226 generate_and_save_waves: model.decode(codes, level)): draws the codes of every
         level (sample_kwargs: total_length, hop_lengths, temperature, top_k, top_p, best_of — the draw is sample()'s,
         seeds included), then renders level `level`'s codes to 16-bit PCM in chunks of chunk_codes codes (VQVAE.render).
         Returns (pcm (n_samples, codes * hop) int16, clipped (n_samples,) int32, zs). The sampler and the VQ-VAE
         must have the same levels and hop lengths; codes outside the codebook — the start token of a prior whose
-        bins exceed num_embeddings — raise VQVAE.render's ValueError."""
+        bins exceed num_embeddings — raise VQVAE.render's ValueError. averaged=True: sample(averaged=True), and the
+        render runs under the VQ-VAE's averaged_weights(); a prior or a VQ-VAE without an average is a ValueError
+        before anything is drawn."""
         if vqvae.levels != self.levels:
             raise ValueError(f"sample_audio: the VQ-VAE has {vqvae.levels} levels, the sampler {self.levels}")
         hops = [int(h) for h in vqvae.decode_hops]
@@ -117,9 +127,20 @@ class VQVAESampler:
             raise ValueError(f"sample_audio: level {level} outside [0, {self.levels})")
         if sample_kwargs.get("return_logprobs"):
             raise ValueError("sample_audio returns no log-probabilities: call sample(return_logprobs=True)")
-        zs = self.sample(n_samples, y_genre=y_genre, seed=seed, **sample_kwargs)
-        pcm, clipped = vqvae.render(zs[level], level, chunk_codes=chunk_codes, gain=gain)
+        if averaged:
+            self._check_averaged(self.priors + [vqvae])
+        zs = self.sample(n_samples, y_genre=y_genre, seed=seed, averaged=averaged, **sample_kwargs)
+        with vqvae.averaged_weights() if averaged else nullcontext():
+            pcm, clipped = vqvae.render(zs[level], level, chunk_codes=chunk_codes, gain=gain)
         return pcm, clipped, zs
+
+    @staticmethod
+    def _check_averaged(models):
+        for m in models:
+            if m.optimizer is None or not m.optimizer.averaging:
+                what = f"the level {m.level} prior" if isinstance(m, Prior) else "the VQ-VAE"
+                raise ValueError(f"averaged=True: {what}'s optimizer keeps no average of the weights "
+                                 "(vqa_optim.Adam(average_decay=...))")
 
     def _plan(self, total_length, hop_lengths):
         """(codes per level, hop per level) of a sample() call, checked before anything is drawn: every window
@@ -155,7 +176,7 @@ class VQVAESampler:
         return starts
 
     def sample_level(self, zs, level, y_genre=None, seed=0, total_length=None, hop_length=None, temperature=1.0,
-                     top_k=0, top_p=1.0, return_logprobs=False):
+                     top_k=0, top_p=1.0, return_logprobs=False, averaged=False):
         """Sampler.py:116-124 (a stub in the reference): draw level `level` given the levels above it in zs and
         return zs with that level filled. total_length: this level's codes (default one window), hop_length: the
         distance of its window starts (default n_ctx // 2).
@@ -165,8 +186,16 @@ class VQVAESampler:
         a training window, its noise seeded seed + level + levels * w (window 0 keeps the one-window seed). Only
         the codes past the prime are appended. A failed launch raises; no later window is queued.
         return_logprobs: returns (zs, (logp_model, logp_draw)), (n_samples, total) fp32 each, sliced from every
-        window's log-probabilities exactly as its codes are (Prior.sample; start token and prime removed)."""
+        window's log-probabilities exactly as its codes are (Prior.sample; start token and prime removed).
+        averaged=True: the windows are drawn under this prior's averaged_weights() (the conditioner, part of the
+        prior's store, included)."""
         pr = self.priors[level]
+        with pr.averaged_weights() if averaged else nullcontext():
+            return self._sample_level(pr, zs, level, y_genre, seed, total_length, hop_length, temperature, top_k,
+                                      top_p, return_logprobs)
+
+    def _sample_level(self, pr, zs, level, y_genre, seed, total_length, hop_length, temperature, top_k, top_p,
+                      return_logprobs):
         n_ctx = pr.context_length
         total = n_ctx if total_length is None else int(total_length)
         hop = max(1, n_ctx // 2) if hop_length is None else int(hop_length)

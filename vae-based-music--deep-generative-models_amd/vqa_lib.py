@@ -49,6 +49,7 @@ EXPORTED = [
     "vqa_resample", "vqa_resample_route",
     "vqa_attn_weights_elems", "vqa_attn_weights",
     "vqa_grad_norm", "vqa_grad_norm_workspace", "vqa_adam_keras_clipped",
+    "vqa_adam_keras_ema", "vqa_adam_keras_clipped_ema", "vqa_swap_f32",
 ]
 
 
@@ -97,6 +98,10 @@ _SIGS = {
     "vqa_grad_norm_workspace": (_S, [_L, _I]),
     "vqa_adam_keras_clipped": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _F, _F, _F, _F, _P, _P, _I, _I, _F, _F, _F, _P,
                                     _P, _P]),
+    "vqa_adam_keras_ema": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _F, _F, _F, _F, _P, _F, _L, _I, _P]),
+    "vqa_adam_keras_clipped_ema": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _F, _F, _F, _F, _P, _P, _I, _I, _F, _F, _F, _P,
+                                        _P, _P, _F, _L, _I, _P]),
+    "vqa_swap_f32": (_I, [_P, _P, _L, _P]),
     "vqa_lr_schedule": (_I, [_P, _P, _I, _F, _F, _F, _F, _P]),
     "vqa_counter_add": (_I, [_P, _L, _P]),
     "vqa_step_metrics": (_I, [_P, _P, _P, _I, _F, _P]),
@@ -546,6 +551,33 @@ def adam_keras_clipped(w, g, m, v, step, lr, beta1, beta2, eps, grad_scale, seg_
                                         beta1, beta2, eps, grad_scale, ptr(seg_start), ptr(block_seg),
                                         seg_start.numel(), int(modes), clipvalue, clipnorm, global_clipnorm,
                                         ptr(seg_norm), ptr(stats), stream()), "vqa_adam_keras_clipped")
+
+
+def adam_keras_ema(w, g, m, v, step, lr, beta1, beta2, eps, grad_scale, ema, average_decay, start_step=0,
+                   dynamic=False, lr_dev=None):
+    """adam_keras with the weights' moving average `ema` updated in the same launch (vqa_adam_keras_ema)."""
+    _check(lib().vqa_adam_keras_ema(ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), ptr(step), float(lr), ptr(lr_dev),
+                                    beta1, beta2, eps, grad_scale, ptr(ema), float(average_decay), int(start_step),
+                                    int(bool(dynamic)), stream()), "vqa_adam_keras_ema")
+
+
+def adam_keras_clipped_ema(w, g, m, v, step, lr, beta1, beta2, eps, grad_scale, seg_start, block_seg, modes,
+                           clipvalue, clipnorm, global_clipnorm, seg_norm, stats, ema, average_decay, start_step=0,
+                           dynamic=False, lr_dev=None):
+    """adam_keras_clipped with the weights' moving average in the same launch (vqa_adam_keras_clipped_ema)."""
+    _check(lib().vqa_adam_keras_clipped_ema(ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), ptr(step), float(lr),
+                                            ptr(lr_dev), beta1, beta2, eps, grad_scale, ptr(seg_start),
+                                            ptr(block_seg), seg_start.numel(), int(modes), clipvalue, clipnorm,
+                                            global_clipnorm, ptr(seg_norm), ptr(stats), ptr(ema),
+                                            float(average_decay), int(start_step), int(bool(dynamic)), stream()),
+           "vqa_adam_keras_clipped_ema")
+
+
+def swap_f32(a, b):
+    """Exchange the contents of two fp32 buffers of equal size in place, exactly (vqa_swap_f32)."""
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.numel() != b.numel():
+        raise VQAError("swap_f32: two float32 buffers of equal size")
+    _check(lib().vqa_swap_f32(ptr(a), ptr(b), a.numel(), stream()), "vqa_swap_f32")
 
 
 def lr_schedule(step, lr_out, kind, p):

@@ -14,6 +14,13 @@ vqa_adam_keras_clipped), so a captured step replays them; nothing is read back. 
 rewritten. Deviation from Keras: a threshold of 0 (which Keras accepts and which zeroes every gradient) is
 refused, as is any value that is not finite and > 0. The thresholds are configuration, not state: checkpoints
 hold nothing of them.
+
+Weight averaging is tensorflow_addons' MovingAverage wrapper folded into the step: with `average_decay` set, the
+Adam launch also updates `average`, an exponential moving average of the flat parameter buffer (DESIGN.md states the
+rule), keyed by the same device step count as a learning-rate schedule, so a captured step replays it.
+`average_start_step` and `dynamic_average_decay` are tfa's start_step and dynamic_decay. assign_average_vars and
+swap_weights carry tfa's names; swap_weights exchanges contents exactly (vqa_swap_f32). The three settings are
+configuration like the thresholds; the average itself is state and travels in checkpoints.
 """
 from __future__ import annotations
 
@@ -41,6 +48,24 @@ def _threshold(name, value):
     return c
 
 
+def _average_settings(decay, start_step, dynamic):
+    """(decay or None, start step, dynamic) checked as the constructor's arguments."""
+    if decay is None:
+        if start_step != 0 or dynamic:
+            raise ValueError("average_start_step and dynamic_average_decay need average_decay "
+                             f"(got average_start_step={start_step!r}, dynamic_average_decay={dynamic!r})")
+        return None, 0, False
+    try:
+        d = float(decay)
+    except (TypeError, ValueError):
+        raise ValueError(f"average_decay: a finite number in [0, 1) or None (got {decay!r})") from None
+    if isinstance(decay, bool) or not (math.isfinite(d) and 0.0 <= d < 1.0):
+        raise ValueError(f"average_decay: a finite number in [0, 1) or None (got {decay!r})")
+    if isinstance(start_step, bool) or not isinstance(start_step, (int, np.integer)) or start_step < 0:
+        raise ValueError(f"average_start_step: an integer >= 0 (got {start_step!r})")
+    return d, int(start_step), bool(dynamic)
+
+
 def clip_tables(offsets, size: int):
     """The variable table of vqa_grad_norm / vqa_adam_keras_clipped for a ParamStore layout (host, numpy):
     seg_start (int64, one ascending offset per variable) and block_seg (int32, per block of V.CLIP_BLOCK floats the
@@ -56,7 +81,8 @@ def clip_tables(offsets, size: int):
 
 class Adam:
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, *, clipvalue=None,
-                 clipnorm=None, global_clipnorm=None, **kwargs):
+                 clipnorm=None, global_clipnorm=None, average_decay=None, average_start_step=0,
+                 dynamic_average_decay=False, **kwargs):
         if callable(learning_rate) and not isinstance(learning_rate, LearningRateSchedule):
             # a host callable cannot be evaluated inside a replayed hipGraph
             raise TypeError("learning_rate: a float or a schedules.LearningRateSchedule (device-evaluated)")
@@ -67,8 +93,11 @@ class Adam:
         self.clipvalue = _threshold("clipvalue", clipvalue)
         self.clipnorm = _threshold("clipnorm", clipnorm)
         self.global_clipnorm = _threshold("global_clipnorm", global_clipnorm)
+        self.average_decay, self.average_start_step, self.dynamic_average_decay = _average_settings(
+            average_decay, average_start_step, dynamic_average_decay)
         self.iterations = None
         self.m = self.v = None
+        self.average = None  # the weights' moving average, a flat buffer like store.flat (build)
         self._lr_dev = None
         self._clip = None  # device tables, norms, statistics and workspace of the clipped path (build)
 
@@ -81,12 +110,18 @@ class Adam:
         return ((V.CLIP_VALUE if self.clipvalue is not None else 0) | (V.CLIP_NORM if self.clipnorm is not None else 0)
                 | (V.CLIP_GLOBAL_NORM if self.global_clipnorm is not None else 0))
 
+    @property
+    def averaging(self) -> bool:
+        return self.average_decay is not None
+
     def build(self, store):
         dev = store.flat.device
         self.m = torch.zeros_like(store.flat)
         self.v = torch.zeros_like(store.flat)
         self.iterations = torch.zeros(1, dtype=torch.int64, device=dev)
         self._lr_dev = torch.zeros(1, dtype=torch.float32, device=dev) if self.scheduled else None
+        # allocated once (a captured step keeps the pointer); starts as the weights, as tfa's slot does
+        self.average = store.flat.detach().clone() if self.averaging else None
         if self.clip_modes:
             # allocated once: a captured step keeps these pointers
             seg, block_seg = clip_tables(store.offsets, store.size)
@@ -127,15 +162,43 @@ class Adam:
         else:
             lr = self.learning_rate
         g = store.grad[:store.size]
+        avg = (self.average, self.average_decay, self.average_start_step, self.dynamic_average_decay)
         if not self.clip_modes:
-            V.adam_keras(store.flat, g, self.m, self.v, self.iterations, lr,
-                         self.beta_1, self.beta_2, self.epsilon, grad_scale, lr_dev=self._lr_dev)
+            if self.averaging:
+                V.adam_keras_ema(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2,
+                                 self.epsilon, grad_scale, *avg, lr_dev=self._lr_dev)
+            else:
+                V.adam_keras(store.flat, g, self.m, self.v, self.iterations, lr,
+                             self.beta_1, self.beta_2, self.epsilon, grad_scale, lr_dev=self._lr_dev)
         else:
             c = self._clip
             thr = (self.clipvalue or 0.0, self.clipnorm or 0.0, self.global_clipnorm or 0.0)
             V.grad_norm(g, c["seg_start"], c["block_seg"], grad_scale, self.clip_modes, *thr, c["seg_norm"],
                         c["stats"], c["ws"])
-            V.adam_keras_clipped(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2,
-                                 self.epsilon, grad_scale, c["seg_start"], c["block_seg"], self.clip_modes, *thr,
-                                 c["seg_norm"], c["stats"], lr_dev=self._lr_dev)
+            if self.averaging:
+                V.adam_keras_clipped_ema(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2,
+                                         self.epsilon, grad_scale, c["seg_start"], c["block_seg"], self.clip_modes,
+                                         *thr, c["seg_norm"], c["stats"], *avg, lr_dev=self._lr_dev)
+            else:
+                V.adam_keras_clipped(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2,
+                                     self.epsilon, grad_scale, c["seg_start"], c["block_seg"], self.clip_modes, *thr,
+                                     c["seg_norm"], c["stats"], lr_dev=self._lr_dev)
         V.counter_add(self.iterations, 1)
+
+    def _averaged(self, what, store):
+        if not self.averaging:
+            raise ValueError(f"{what}: the optimizer keeps no average (average_decay=None)")
+        if self.average is None:
+            self.build(store)
+        return self.average
+
+    def assign_average_vars(self, store):
+        """tfa's assign_average_vars: the weights become a copy of their average (the average stays)."""
+        average = self._averaged("assign_average_vars", store)
+        store.flat.copy_(average)
+
+    def swap_weights(self, store):
+        """tfa's swap_weights: the weights and their average change places, exactly (vqa_swap_f32; no temporary).
+        A second call restores both bitwise."""
+        average = self._averaged("swap_weights", store)
+        V.swap_f32(store.flat, average)

@@ -1,6 +1,8 @@
-"""What the VQ-VAE and prior trainers share: the train step as a replayable hipGraph, and the optimizer's half of a
-checkpoint. What differs between the models stays with them: their inputs and checks, and what surrounds a replay."""
+"""What the VQ-VAE and prior trainers share: the train step as a replayable hipGraph, the optimizer's half of a
+checkpoint, and the context in which a model runs on the moving average of its weights. What differs between the models stays with them: their inputs and checks, and what surrounds a replay."""
 from __future__ import annotations
+
+from contextlib import contextmanager
 
 import torch
 
@@ -68,19 +70,60 @@ class CapturedStep:
             g2.replay()
 
 
+@contextmanager
+def averaged_weights(model, store):
+    """The body runs on the optimizer's moving average of `store`'s weights: the contents of the two buffers change
+    places on entry and change back on exit (Adam.swap_weights, exact), also when the body raises. No pointer moves,
+    so captured graphs and per-call weight images see the averaged weights inside and the trained ones after."""
+    opt = model.optimizer
+    if opt is None or not opt.averaging:
+        raise ValueError("averaged_weights: the model's optimizer keeps no average (compile with "
+                         "vqa_optim.Adam(average_decay=...))")
+    if model._in_average:
+        raise RuntimeError("averaged_weights: already inside the context")
+    opt.swap_weights(store)
+    model._in_average = True
+    try:
+        yield model
+    finally:
+        opt.swap_weights(store)
+        model._in_average = False
+
+
+def refuse_averaged(model, what):
+    """Training and saving act on the trained weights: refused, before any launch, while they hold the average."""
+    if model._in_average:
+        raise RuntimeError(f"{what}: not inside averaged_weights() (the weights hold their moving average)")
+
+
 def adam_state(optimizer) -> dict:
-    """The optimizer's entries of a checkpoint: both moments (host copies) and the step count."""
-    return {"adam_m": optimizer.m.detach().cpu().clone(), "adam_v": optimizer.v.detach().cpu().clone(),
-            "iterations": int(optimizer.iterations.item())}
+    """The optimizer's entries of a checkpoint: both moments (host copies), the step count and, when it keeps one,
+    the weights' moving average."""
+    sd = {"adam_m": optimizer.m.detach().cpu().clone(), "adam_v": optimizer.v.detach().cpu().clone(),
+          "iterations": int(optimizer.iterations.item())}
+    if optimizer.average is not None:
+        sd["adam_ema"] = optimizer.average.detach().cpu().clone()
+    return sd
 
 
 def adam_from_checkpoint(ck, store, layout, path) -> dict:
-    """Those entries of the checkpoint dict `ck`, the moments brought into `store`'s layout."""
-    return {"adam_m": store.from_layout(ck["adam_m"], layout, f"{path} (adam_m)"),
-            "adam_v": store.from_layout(ck["adam_v"], layout, f"{path} (adam_v)"), "iterations": ck["iterations"]}
+    """Those entries of the checkpoint dict `ck`, the moments (and the average) brought into `store`'s layout."""
+    sd = {"adam_m": store.from_layout(ck["adam_m"], layout, f"{path} (adam_m)"),
+          "adam_v": store.from_layout(ck["adam_v"], layout, f"{path} (adam_v)"), "iterations": ck["iterations"]}
+    if "adam_ema" in ck:
+        sd["adam_ema"] = store.from_layout(ck["adam_ema"], layout, f"{path} (adam_ema)")
+    return sd
 
 
-def set_adam_state(optimizer, sd, device):
+def set_adam_state(optimizer, sd, device, store=None):
+    """`store` holds the weights already loaded: an averaging optimizer given a state without an average (a file
+    written without averaging) starts its average from them. An average given to an optimizer that keeps none is
+    ignored."""
     optimizer.m.copy_(sd["adam_m"].to(device))
     optimizer.v.copy_(sd["adam_v"].to(device))
     optimizer.iterations.fill_(int(sd["iterations"]))
+    if optimizer.average is not None:
+        if "adam_ema" in sd:
+            optimizer.average.copy_(sd["adam_ema"].to(device))
+        elif store is not None:
+            optimizer.average.copy_(store.flat)

@@ -38,7 +38,8 @@ from vqa_layers import CKPT_VERSION, ParamStore, checkpoint_layout
 from vqa_metrics import SlotMean
 from vqa_module import keras_evaluate, keras_fit_feed
 from vqa_optim import Adam
-from vqa_train import CapturedStep, adam_from_checkpoint, adam_state, set_adam_state
+from vqa_train import (CapturedStep, adam_from_checkpoint, adam_state, averaged_weights, refuse_averaged,
+                       set_adam_state)
 from VectorQuantizer import VectorQuantizer
 
 
@@ -258,6 +259,7 @@ class VQVAE:
         self.vqvaes = [LevelModel(self.input_shape, self.encoders[l], self.decoders[l], self.vqs[l], l, owner=self)
                        for l in range(levels)]
         self._captured: Optional[CapturedStep] = None
+        self._in_average = False  # inside averaged_weights()
         # run the levels' independent forward/backward chains on one stream each (VQA_LEVEL_STREAMS=0: serial)
         self.concurrent_levels = os.environ.get("VQA_LEVEL_STREAMS", "1") != "0"
         self._streams = None
@@ -269,9 +271,18 @@ class VQVAE:
     def compile(self, optimizer=None, **kwargs):
         """keras Model.compile: a vqa_optim.Adam (float or LearningRateSchedule learning rate). A captured step
         is dropped: it holds the previous optimizer's buffers (m, v, step counter, learning rate)."""
+        refuse_averaged(self, "compile")
         self.optimizer = optimizer or Adam()
         self.optimizer.build(self.store)
         self._captured = None
+
+    def averaged_weights(self):
+        """`with model.averaged_weights():` runs the body on the moving average of the weights that an optimizer built
+        with average_decay keeps (vqa_optim.Adam): evaluate, test_step, __call__, encode*, decode*, render and
+        get_weights see the averaged weights; on exit, also by an exception, the trained weights are back bitwise.
+        train_step, fit, capture_train_step, compile, save, load and entering again raise RuntimeError inside, before
+        anything is launched. ValueError when the optimizer keeps no average."""
+        return averaged_weights(self, self.store)
 
     # None or the captured (g1, g2), g2 None in the one-graph form; the AudioFeed the step draws from (None: a copy-in)
     _graph = property(lambda self: self._captured and self._captured.graphs)
@@ -461,6 +472,7 @@ class VQVAE:
 
     def train_step(self, data):
         """vqvae.py:111-146. Returns the running-mean metric dict (0-dim device tensors)."""
+        refuse_averaged(self, "train_step")
         if self.optimizer is None:
             self.compile()
         if isinstance(data, AudioFeed):
@@ -507,6 +519,7 @@ class VQVAE:
         x_example may be an audio_feed.AudioFeed: its gather launch and counter increment are then recorded at the
         head of the graph and the graph's input is the feed's own buffer (no copy); the warm-up steps draw (and
         consume) feed steps, and a later train_step(feed) with this feed replays."""
+        refuse_averaged(self, "capture_train_step")
         if self.optimizer is None:
             self.compile()
         feed = x_example if isinstance(x_example, AudioFeed) else None
@@ -716,6 +729,7 @@ class VQVAE:
         """Minimal keras fit: `self.metrics` reset per epoch (keras semantics); returns the history of
         epoch-end results. With an audio_feed.AudioFeed as x an epoch is the feed's steps_per_epoch steps (graph
         replays once the step is captured with that feed); batch size, shuffling and seed are the feed's."""
+        refuse_averaged(self, "fit")
         if self.optimizer is None:
             self.compile()
         if isinstance(x, AudioFeed):
@@ -764,7 +778,9 @@ class VQVAE:
         ckpt_interval epochs, src/callback/vae_monitor.py:56-58): tensors, ints and strings only, so
         `torch.load(path, weights_only=True)` reads it. Holds the weights, Adam moments and step, and each
         level's codebook E, m_t, N_t and reset counter: resuming reproduces the uninterrupted run bit for
-        bit (every reduction of the step runs in a fixed order)."""
+        bit (every reduction of the step runs in a fixed order). An optimizer that averages the weights adds the
+        average (adam_ema)."""
+        refuse_averaged(self, "save")
         sd = self.state_dict()
         out = {"format": f"vqa-vqvae/{CKPT_VERSION}", "param_names": [n for n, _, _ in self.store.specs],
                "layout": self.store.layout_record(),
@@ -772,7 +788,7 @@ class VQVAE:
                           "latent_dim": self.latent_dim, "num_embeddings": self.num_embeddings,
                           "down_depth": list(self.down_depth), "strides": list(self.strides)},
                "weights": sd["weights"]}
-        for k in ("adam_m", "adam_v", "iterations"):
+        for k in ("adam_m", "adam_v", "adam_ema", "iterations"):
             if k in sd:
                 out[k] = sd[k]
         for l, st in enumerate(sd["vq"]):
@@ -784,7 +800,10 @@ class VQVAE:
     def load(self, path: str):
         """Restore a `save` checkpoint (loaded weights-only: nothing in the file is executed). Format /2 records
         each tensor's offset, and the weights and Adam moments are copied tensor by tensor into this model's
-        layout; a /1 file is read in the layout its length identifies (aligned or the earlier packed one)."""
+        layout; a /1 file is read in the layout its length identifies (aligned or the earlier packed one). A file
+        without a weight average loaded into an averaging optimizer starts the average from the loaded weights; a
+        file's average is ignored by an optimizer that keeps none."""
+        refuse_averaged(self, "load")
         ck = torch.load(path, map_location="cpu", weights_only=True)
         lay = checkpoint_layout(ck, self.store, "vqvae", path)
         if ck.get("config", {}).get("levels", self.levels) != self.levels:
@@ -802,4 +821,6 @@ class VQVAE:
         if "adam_m" in sd:
             if self.optimizer is None:
                 self.compile()
-            set_adam_state(self.optimizer, sd, self.device)
+            set_adam_state(self.optimizer, sd, self.device, self.store)
+        elif self.optimizer is not None and self.optimizer.average is not None:
+            self.optimizer.average.copy_(self.store.flat)
