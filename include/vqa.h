@@ -464,6 +464,26 @@ int vqa_code_batch(const void* codes, int64_t codes_len, const void* upper /* ma
  * 4-byte aligned; a gain that is not finite and >= 0. */
 int vqa_pcm_encode(const float* x, int64_t ldx, int16_t* out, int64_t ldo, int B, int64_t x0, int64_t o0, int64_t n,
                    float gain, int32_t* clipped /* may be NULL */, vqa_stream_t stream);
+/* vqa_pcm_encode with a second source and a seam: the render of a continued recording. p (B, ldp) fp32 is the prompt
+ * audio, indexed by absolute position in the piece (as out is); seam is the absolute sample index where the prompt
+ * ends and fade, 0 <= fade <= seam, the length of the cross-fade in front of it. For the output sample at absolute
+ * position t = o0 + j, with b = x[row][x0 + j]:
+ *   t >= seam:          s = b
+ *   t <  seam - fade:   s = p[row][t]
+ *   otherwise:          i = t - (seam - fade), w = float(i + 1) / float(fade + 1), a = p[row][t],
+ *                       s = a + (b - a) * w    the difference, the quotient, the product and the sum each rounded in
+ *                                              fp32 (no fma contraction): w rises from 1/(fade+1) to fade/(fade+1)
+ *   v = (s * gain) * 32768, then the rounding, the clamp, the NaN rule and the clipped count of vqa_pcm_encode.
+ * A launch wholly at or past the seam writes what vqa_pcm_encode writes, bit for bit.
+ * Memory contract: x is read only on [x0, x0 + n) of a row and there only where t >= seam - fade; p is read only on
+ * [o0, o0 + n) ∩ [0, seam); out is written only on [o0, o0 + n). x0, o0, seam and fade are arbitrary: the seam and
+ * the fade may fall in a row's scalar head, inside one of its 16-byte stores or in its tail. A fade longer than n is
+ * rendered by consecutive launches, each with the same seam and fade.
+ * VQA_E_INVALID_ARG before any launch (messages start "pcm_splice:"): everything vqa_pcm_encode rejects; a null p;
+ * seam < 0; fade outside [0, seam]; ldp < min(seam, o0 + n); p not 4-byte aligned. */
+int vqa_pcm_splice(const float* x, int64_t ldx, const float* p, int64_t ldp, int16_t* out, int64_t ldo, int B,
+                   int64_t x0, int64_t o0, int64_t n, int64_t seam, int64_t fade, float gain,
+                   int32_t* clipped /* may be NULL */, vqa_stream_t stream);
 
 /* Polyphase sample-rate conversion by up / down (coprime: L = sr_out / g, M = sr_in / g, g = gcd of the rates) with
  * a caller-supplied fp32 tap table `taps` (up, taps_per_phase), row-major. With P = taps_per_phase and W = P / 2,

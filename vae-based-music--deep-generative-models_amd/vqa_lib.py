@@ -45,7 +45,7 @@ EXPORTED = [
     "vqa_axpy", "vqa_dropout", "vqa_scale_f32", "vqa_tf_mix", "vqa_attn_fwd", "vqa_attn_bwd", "vqa_head_wt",
     "vqa_head_fwd", "vqa_head_bwd_workspace", "vqa_head_bwd", "vqa_rowsum_workspace", "vqa_rowsum", "vqa_prior_decode_cache_bytes",
     "vqa_prior_decode", "vqa_prior_decode_primed", "vqa_prior_decode_filtered", "vqa_prior_decode_scored",
-    "vqa_corpus_steps_per_epoch", "vqa_corpus_batch", "vqa_pcm_encode", "vqa_code_batch",
+    "vqa_corpus_steps_per_epoch", "vqa_corpus_batch", "vqa_pcm_encode", "vqa_pcm_splice", "vqa_code_batch",
     "vqa_resample", "vqa_resample_route",
     "vqa_attn_weights_elems", "vqa_attn_weights",
     "vqa_grad_norm", "vqa_grad_norm_workspace", "vqa_adam_keras_clipped",
@@ -174,6 +174,7 @@ _SIGS = {
     "vqa_code_batch": (_I, [_P, _L, _P, _L, _I, _I, _P, _P, _L, _P, _P, _P, _P, _I, _L, _U, _P, _L, _I, _I, _I, _P]),
     # waveform -> int16 PCM
     "vqa_pcm_encode": (_I, [_P, _L, _P, _L, _I, _L, _L, _L, _F, _P, _P]),
+    "vqa_pcm_splice": (_I, [_P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _L, _L, _F, _P, _P]),
     # polyphase sample-rate conversion
     "vqa_resample": (_I, [_P, _I, _L, _L, _L, _L, _P, _L, _L, _L, _I, _I, _I, _P, _I, _P]),
     "vqa_resample_route": (_I, [_I, _I, _I, _P, _P]),
@@ -739,6 +740,28 @@ def pcm_encode(x, out, x0=0, o0=0, n=None, gain=1.0, clipped=None):
     n = ldx - int(x0) if n is None else int(n)
     _check(lib().vqa_pcm_encode(ptr(x), ldx, ptr(out), ldo, B, int(x0), int(o0), n, float(gain), ptr(clipped),
                                 stream()), "vqa_pcm_encode")
+
+
+def pcm_splice(x, p, out, seam, fade=0, x0=0, o0=0, n=None, gain=1.0, clipped=None):
+    """pcm_encode with a second source and a seam (vqa_pcm_splice, include/vqa.h): p is the (B, ldp) or (B, ldp, 1)
+    fp32 prompt audio, indexed by absolute position as out is. The samples of out at [o0, o0 + n) are p before
+    seam - fade, x from seam on and, over the `fade` samples between, p + (x - p) * (i + 1) / (fade + 1); then
+    pcm_encode's gain, rounding, clamp and clipped count."""
+    if x.dtype != torch.float32 or p.dtype != torch.float32 or out.dtype != torch.int16:
+        raise VQAError(f"pcm_splice: x and p are float32 and out int16 (got {x.dtype}, {p.dtype}, {out.dtype})")
+    B = x.shape[0] if x.dim() > 1 else 1
+    ldx = x.numel() // max(B, 1)
+    Bp = p.shape[0] if p.dim() > 1 else 1
+    ldp = p.numel() // max(Bp, 1)
+    Bo = out.shape[0] if out.dim() > 1 else 1
+    ldo = out.numel() // max(Bo, 1)
+    if Bo != B or Bp != B:
+        raise VQAError(f"pcm_splice: x has {B} rows, p {Bp}, out {Bo}")
+    if clipped is not None and (clipped.dtype != torch.int32 or clipped.numel() != B):
+        raise VQAError(f"pcm_splice: clipped holds {B} int32 entries")
+    n = ldx - int(x0) if n is None else int(n)
+    _check(lib().vqa_pcm_splice(ptr(x), ldx, ptr(p), ldp, ptr(out), ldo, B, int(x0), int(o0), n, int(seam), int(fade),
+                                float(gain), ptr(clipped), stream()), "vqa_pcm_splice")
 
 
 RESAMPLE_F32, RESAMPLE_I16 = 0, 1  # x_dtype of vqa_resample

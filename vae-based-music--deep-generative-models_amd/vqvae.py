@@ -682,12 +682,16 @@ class VQVAE:
             raise ValueError(f"{what}: code {bad} outside [0, {K}){hint}")
         return zq
 
-    def _decode_chunks(self, zq, level, chunk_codes):
+    def _decode_chunks(self, zq, level, chunk_codes, known_codes=0):
         """(in_lo, core_lo, core_hi, audio) of every chunk of decode_plan, audio = the decoder's fp32 (B, L hop, 1)
-        output for the codes [in_lo, in_hi) — one chunk's activations alive at a time, nothing saved."""
+        output for the codes [in_lo, in_hi) — one chunk's activations alive at a time, nothing saved. A chunk whose
+        core ends at or before known_codes is not decoded: its audio is None."""
         dec, vq = self.decoders[level], self.vqs[level]
         B, T = zq.shape
         for in_lo, in_hi, core_lo, core_hi in decode_plan(T, chunk_codes, decoder_halo(dec)):
+            if core_hi <= known_codes:
+                yield in_lo, core_lo, core_hi, None
+                continue
             idx = zq[:, in_lo:in_hi].contiguous()
             q = torch.empty(B, in_hi - in_lo, self.latent_dim, dtype=self.cdt, device=self.device)
             V.embedding_fwd(vq.ET, idx, q)  # one_hot(zq) @ E^T as a row gather, straight into the compute dtype
@@ -706,23 +710,62 @@ class VQVAE:
                 y[:, core_lo * hop:core_hi * hop] = r[:, (core_lo - in_lo) * hop:(core_hi - in_lo) * hop]
         return y
 
-    def render(self, zq, level=0, chunk_codes=4096, gain=1.0):
+    def render(self, zq, level=0, chunk_codes=4096, gain=1.0, prompt_audio=None, fade_samples=0):
         """Codes to 16-bit PCM: -> (pcm (B, T hop) int16, clipped (B,) int32), both on the device. The chunks of
         decode_chunked, each core cropped out of its chunk, scaled by `gain`, rounded half to even, clamped and
         placed by one vqa_pcm_encode launch; clipped[b] counts the samples of item b that were clamped (or NaN).
-        The full-length fp32 waveform is never formed."""
+        The full-length fp32 waveform is never formed.
+
+        prompt_audio (B, T_p) or (B, T_p, 1) fp32 on the device, T_p a multiple of the level's hop and at most the
+        piece's length: the piece starts with these samples themselves, not with their reconstruction. The seam is
+        at T_p; over the fade_samples samples in front of it (0 <= fade_samples <= T_p) the prompt fades linearly
+        into the decode (vqa_pcm_splice). A chunk whose core ends at or before seam - fade_samples is a copy of the
+        prompt and is not decoded; one that starts at or after the seam is a vqa_pcm_encode launch as without a
+        prompt. ValueError for a bad prompt or fade before anything is launched."""
         zq = self._checked_codes(zq, "render")
         gain = float(gain)
         if not (np.isfinite(gain) and gain >= 0.0):
             raise ValueError(f"render: gain {gain} must be finite and >= 0")
         hop = self.decoders[level].receptive_reach()[1]
+        if prompt_audio is None:
+            if fade_samples:
+                raise ValueError("render: fade_samples needs prompt_audio")
+            seam = fade = 0
+        else:
+            prompt_audio, seam, fade = self._checked_prompt(prompt_audio, fade_samples, zq.shape[0],
+                                                            zq.shape[1] * hop, hop)
         pcm = torch.empty(zq.shape[0], zq.shape[1] * hop, dtype=torch.int16, device=self.device)
         clipped = torch.zeros(zq.shape[0], dtype=torch.int32, device=self.device)
         with torch.no_grad():
-            for in_lo, core_lo, core_hi, r in self._decode_chunks(zq, level, chunk_codes):
-                V.pcm_encode(r, pcm, x0=(core_lo - in_lo) * hop, o0=core_lo * hop, n=(core_hi - core_lo) * hop,
-                             gain=gain, clipped=clipped)
+            for in_lo, core_lo, core_hi, r in self._decode_chunks(zq, level, chunk_codes, (seam - fade) // hop):
+                x0, o0, n = (core_lo - in_lo) * hop, core_lo * hop, (core_hi - core_lo) * hop
+                if o0 >= seam:
+                    V.pcm_encode(r, pcm, x0=x0, o0=o0, n=n, gain=gain, clipped=clipped)
+                elif r is None:  # a copy of the prompt: x is never read, the prompt's own rows stand in for it
+                    V.pcm_splice(prompt_audio, prompt_audio, pcm, seam, fade, x0=o0, o0=o0, n=n, gain=gain,
+                                 clipped=clipped)
+                else:
+                    V.pcm_splice(r, prompt_audio, pcm, seam, fade, x0=x0, o0=o0, n=n, gain=gain, clipped=clipped)
         return pcm, clipped
+
+    def _checked_prompt(self, prompt_audio, fade_samples, B, total, hop):
+        """(prompt (B, T_p) fp32 contiguous on the device, seam, fade) of a render call, or ValueError."""
+        p = prompt_audio
+        if not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.float32:
+            raise ValueError("render: prompt_audio must be a float32 device tensor")
+        if p.dim() == 3 and p.shape[-1] == 1:
+            p = p[:, :, 0]
+        if p.dim() != 2 or p.shape[0] != B:
+            raise ValueError(f"render: prompt_audio must be ({B}, T_p) or ({B}, T_p, 1) (got shape "
+                             f"{tuple(prompt_audio.shape)})")
+        seam = int(p.shape[1])
+        if seam < hop or seam % hop or seam > total:
+            raise ValueError(f"render: the prompt's {seam} samples must be a positive multiple of the hop {hop} and at "
+                             f"most the piece's {total}")
+        if isinstance(fade_samples, bool) or not isinstance(fade_samples, (int, np.integer)) \
+                or not 0 <= fade_samples <= seam:
+            raise ValueError(f"render: fade_samples {fade_samples!r} must be an integer in [0, {seam}]")
+        return p.contiguous(), seam, int(fade_samples)
 
     # ------------------------------------------------------------------ training loop / state
     def fit(self, x=None, y=None, batch_size=32, epochs=1, shuffle=True, seed=0, verbose=0):
