@@ -689,6 +689,10 @@ int vqa_rowsum(const float* x, int64_t rows, int64_t n, float scale, float* out,
  * next token = argmax z. tokens (N, steps+1) int64 with tokens[:, 0] = start. Optional: ycond (N, width)
  * label embedding for position 0, xcond (N, ctx, width) fp32 upper-level conditioning, forced (N, steps+1)
  * input tokens (teacher-forced check), logits (N, steps, bins) output. width 128, attention width 32.
+ * The layer descriptors must describe an attention width of 32 (m_attn * width): qkv_kernel (3, 128, 96), qkv_bias
+ * (96), query / key / value / out kernels of 32 x 32 and biases of 32, proj_kernel (32, 128). The entry point is
+ * not told the attention width and cannot check it: it strides every one of these tensors as 32 columns, so a
+ * caller with another m_attn must refuse before the call (vqa_lib.decode_shape_error does, for sample()).
  * out_kernel is (width, out_ld) row-major with out_ld >= bins a multiple of 4 and out_bias has out_ld entries
  * (a vocabulary that is not a multiple of 4, e.g. the sampler's default 513 bins, is passed zero-padded; the
  * padded columns are never sampled).

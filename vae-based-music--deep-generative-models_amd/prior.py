@@ -291,6 +291,7 @@ class FactorizedTransformer:
     def __init__(self, ctc_len, num_heads, depth, d_model, blocks, attn_stacks, m_attn=0.25, m_mlp=1.0, rate=0.1,
                  **kwargs):
         self.d_model, self.depth = d_model, depth
+        self.attn_width = int(d_model * m_attn)  # FactorizedAttention.width of every layer
         self.attn_func = {0: lambda d: [0, 1][d % 2], 1: lambda d: [0, 1, 2][d % 3]}[attn_stacks]
         self.layers = [ResidualAttnBlock(ctc_len, num_heads, d_model, blocks, attn_func=self.attn_func(i),
                                          m_attn=m_attn, m_mlp=m_mlp, rate=rate) for i in range(depth)]
@@ -323,6 +324,11 @@ class FMHABasedAutoregressiveModel:
                  pos_emb=True, downs=None, strides=None, cond_kwargs=None, dtype="fp32", device="cuda", seed=1,
                  store: Optional[ParamStore] = None, prefix="prior", grad_extra: int = 0, label_bins=None, **kwargs):
         self.context_length = int(np.prod(context_length))
+        if not pos_emb and self.context_length > int(maximum_pos_encoding):
+            # autoregressive_fmha.py:136-137 slices the sinusoid table to the sequence; the embedding and decode
+            # kernels index it by position, so a table shorter than the context would be read past its end
+            raise ValueError(f"pos_emb=False: context length {self.context_length} exceeds the sinusoid table of "
+                             f"maximum_pos_encoding={int(maximum_pos_encoding)} rows")
         self.bins, self.d_model, self.depth = target_vocab_size, width, depth
         self.heads, self.blocks = heads, blocks
         self.use_pos_embedding = pos_emb
@@ -397,12 +403,14 @@ class FMHABasedAutoregressiveModel:
         global index of the first (sequence, position) row (data parallel: rank * N * T) — the dropout masks' key.
         attn_weights: (layer indices, dict) — the dict receives 'transformer_layer_{i}_attention' of those layers
         (transformer.py:106-115); None: no layer computes its weights."""
+        N, T = tokens.shape
+        # the embedding kernel reads row t of the position table for every t < T, learned or sinusoid
+        if T > self._pos().shape[0]:
+            raise ValueError(f"sequence of {T} > the {self._pos().shape[0]} rows of the position table "
+                             f"(context length {self.context_length})")
         if not prepped:
             self.prep_weights(bwd=False)
         tokens = tokens.contiguous()
-        N, T = tokens.shape
-        if self.use_pos_embedding and T > self.context_length:
-            raise ValueError(f"sequence of {T} > context length {self.context_length}")
         # the embedding kernel reads x_cond[n, t] (n < N, t < T) and y_cond[n]: check before passing pointers
         if x_cond is not None and (x_cond.dim() != 3 or x_cond.shape[0] != N or x_cond.shape[1] < T
                                    or x_cond.shape[2] != self.d_model):
@@ -537,7 +545,8 @@ class FMHABasedAutoregressiveModel:
             prime = prime.contiguous()
             if prime.numel() and not (int(prime.min()) >= 0 and int(prime.max()) < self.bins):
                 raise ValueError(f"prime values outside [0, {self.bins})")
-        why = V.decode_shape_error(self.context_length, self.heads, self.blocks)
+        why = V.decode_shape_error(self.context_length, self.heads, self.blocks, self.d_model,
+                                   self.transformer.attn_width, self.depth)
         if why is not None:
             raise ValueError(f"sample(): {why}")
         xc = None
@@ -668,7 +677,7 @@ class Prior:
         self.prior = FMHABasedAutoregressiveModel(
             target_vocab_size=bins, width=prior_kwargs["width"], depth=prior_kwargs["depth"],
             heads=prior_kwargs["heads"], blocks=prior_kwargs["blocks"], attn_stacks=prior_kwargs["attn_stacks"],
-            drop_out_rate=prior_kwargs.get("drop_out_rate", 0.1), context_length=self.z_shape, zq_shapes=z_shapes,
+            m_attn=prior_kwargs.get("m_attn", 0.25), drop_out_rate=prior_kwargs.get("drop_out_rate", 0.1), context_length=self.z_shape, zq_shapes=z_shapes,
             level=level, levels=self.levels, downs=down_depth, strides=strides, cond_kwargs=x_cond_kwargs,
             dtype=dtype, device=device, seed=seed, grad_extra=2, label_bins=genre_classes)
         # data parallel (one process per GPU): ONE all_reduce per step over [gradients | loss, accuracy]

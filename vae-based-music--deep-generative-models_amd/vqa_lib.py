@@ -1134,10 +1134,24 @@ class PriorLayerDesc(ctypes.Structure):
 # blocks) floats must fit it, and a block is at most DECODE_MAX_BLOCK_LEN tokens
 DECODE_SCORE_FLOATS = 4096
 DECODE_MAX_BLOCK_LEN = 2048
+# the decode kernel's compile-time shape (kDecW, kDecAW, kDecMaxLayers, vqa_prior_decode.hip): the entry point is told
+# the model width and the depth, but not the attention width its layer descriptors describe
+DECODE_WIDTH = 128
+DECODE_ATTN_WIDTH = 32
+DECODE_MAX_LAYERS = 8
 
 
-def decode_shape_error(ctx, heads, blocks) -> Optional[str]:
-    """None if vqa_prior_decode accepts (ctx, heads, blocks), else the rule it breaks (include/vqa.h)."""
+def decode_shape_error(ctx, heads, blocks, width=DECODE_WIDTH, attn_width=DECODE_ATTN_WIDTH, depth=1) -> Optional[str]:
+    """None if vqa_prior_decode accepts a model of this shape, else the rule it breaks (include/vqa.h). width: the
+    model width; attn_width: int(width * m_attn), the width of the q / k / v heads that the layers' kernels hold —
+    the kernel strides them as 32 columns whatever they are, so only this check can refuse another one."""
+    if width != DECODE_WIDTH:
+        return f"decode supports a model width of {DECODE_WIDTH} (got {width})"
+    if attn_width != DECODE_ATTN_WIDTH:
+        return (f"decode supports an attention width of {DECODE_ATTN_WIDTH} (width * m_attn; got {attn_width}): the "
+                f"kernel reads every layer's q / k / v kernels as {DECODE_ATTN_WIDTH} columns")
+    if not 1 <= depth <= DECODE_MAX_LAYERS:
+        return f"decode supports a depth of 1 to {DECODE_MAX_LAYERS} layers (got {depth})"
     l = ctx // blocks
     if heads not in (1, 2, 4):
         return f"decode supports 1, 2 or 4 heads (got {heads})"
