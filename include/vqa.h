@@ -255,6 +255,14 @@ int vqa_vq_ema_apply(float* E, float* ET, float* m_t, float* N_t, const float* m
 int vqa_vq_ema_apply_derived(float* E, float* ET, float* m_t, float* N_t, const float* m_sumT, const float* n_sum,
                              const float* RT, float gamma, float one_minus_gamma, float thresh, float* metrics,
                              int64_t* counter, float* e_sqnorm, void* E3, int D, int K, vqa_stream_t stream);
+/* vqa_vq_ema_apply_derived behind a device flag: with ok[0] == 1 every output is bitwise that entry point's; otherwise
+ * E, ET, m_t, N_t, *counter, metrics, e_sqnorm and E3 are left untouched. The flag is vqa_grad_finite over the
+ * level's summed statistics (m_sumT | n_sum, after the data-parallel exchange): a codebook is not updated from
+ * sums that hold a NaN or an inf. */
+int vqa_vq_ema_apply_guarded(float* E, float* ET, float* m_t, float* N_t, const float* m_sumT, const float* n_sum,
+                             const float* RT, float gamma, float one_minus_gamma, float thresh, float* metrics,
+                             int64_t* counter, float* e_sqnorm, void* E3, int D, int K, const int32_t* ok,
+                             vqa_stream_t stream);
 /* The reset permutation (host-callable; the device uses the same code): a keyed 4-round Feistel
  * bijection on [0, M) with cycle walking. Returns the k-th sampled row of the tiled batch. */
 int64_t vqa_reset_perm_index(uint64_t seed, int64_t counter, int level, int64_t M, int64_t k);
@@ -354,6 +362,38 @@ int vqa_adam_keras_clipped_ema(float* w, const float* g, float* m, float* v, int
 /* a[i] <-> b[i] for i in [0, n): exact, in place, no temporary (tfa's swap_weights adds and subtracts, which is
  * not exact). a and b must not be the same buffer or overlap. */
 int vqa_swap_f32(float* a, float* b, int64_t n, vqa_stream_t stream);
+/* ---- skipping non-finite steps: a step whose aggregated gradient holds a NaN or an inf is not applied and does
+ *      not advance the step counter (keras' LossScaleOptimizer rule), decided on the device so a captured step
+ *      replays the decision and nothing is read back.
+ * ok[0] = 1 (int32, device) if every one of the n floats of g is finite, else 0. Finite means the exponent field is
+ * not all ones: any finite value however large, denormals and -0.0 pass; NaN and +-inf do not. ok is overwritten on
+ * every call and nothing is kept between calls. Two launches (the 1, then an integer atomic AND: no float atomics,
+ * the result does not depend on scheduling); one grid-stride loop under VQA_FINITE_MAX_BLOCKS workgroups of 256,
+ * 16-byte loads from the first 16-byte boundary of g on, the floats before it and behind the last whole group of
+ * four one by one. g needs 4-byte alignment only. */
+#define VQA_FINITE_MAX_BLOCKS 4096
+int vqa_grad_finite(const float* g, int64_t n, int32_t* ok, vqa_stream_t stream);
+/* The four updates above behind the flag, as one entry point: modes == 0 is vqa_adam_keras[_ema] (the variable
+ * table, seg_norm and stats may be NULL then), any other modes vqa_adam_keras_clipped[_ema]; ema == NULL keeps no
+ * average (average_decay, start_step and dynamic are ignored then). w, g, m, v and ema must be 16-byte aligned in
+ * every form. skip_counters (int64[2], device): [0] steps skipped in all, [1] steps skipped in a row; they must
+ * not alias step.
+ *   ok[0] == 1: w, m, v and ema come out bitwise as from the unguarded entry point with the same arguments;
+ *               skip_counters[1] = 0.
+ *   otherwise : no byte of w, m, v or ema is written; both counters += 1.
+ * Does not touch *step: vqa_counter_add_if(step, 1, ok) follows, so a skipped step leaves the bias correction, the
+ * learning-rate schedule and the average's start step and dynamic decay where they were. */
+int vqa_adam_keras_guarded(float* w, const float* g, float* m, float* v, int64_t n, const int64_t* step, float lr,
+                           const float* lr_dev, float beta1, float beta2, float eps, float grad_scale,
+                           const int64_t* seg_start, const int32_t* block_seg, int nseg, int modes, float clipvalue,
+                           float clipnorm, float global_clipnorm, const float* seg_norm, const float* stats,
+                           float* ema, float average_decay, int64_t start_step, int dynamic, const int32_t* ok,
+                           int64_t* skip_counters, vqa_stream_t stream);
+/* *counter += delta if ok[0] == 1, else nothing. */
+int vqa_counter_add_if(int64_t* counter, int64_t delta, const int32_t* ok, vqa_stream_t stream);
+/* vqa_step_metrics if ok[0] == 1; otherwise every row of macc keeps its total and its count. */
+int vqa_step_metrics_if(const float* loss_slots, const float* vq_metrics, float* macc, int levels, float scale,
+                        const int32_t* ok, vqa_stream_t stream);
 /* keras LearningRateSchedule at the optimizer's device step counter (OptimizerV2._decayed_lr: schedule(float(
  * iterations)), before the step's increment): *lr = f(*step), so a captured train step replays with the right rate.
  * kind 0: p0. kind 1, CustomSchedule (src/transformer/multi_head_attention.py:82-101): p0 = rsqrt(d_model),

@@ -60,6 +60,7 @@ class VectorQuantizer:
         self.usage_tracker = Mean(f"[{level}]codebook_usage", self.device)
         self.entropy_tracker = Mean(f"[{level}]codebook_entropy", self.device)
         self._saved = None
+        self.stats_ok = torch.ones(1, dtype=torch.int32, device=self.device)  # the guarded update's flag
 
     @property
     def metrics(self):
@@ -163,12 +164,24 @@ class VectorQuantizer:
         V.vq_backward(dq.reshape(-1, D), flat, self.ET, idx, dz, float(2.0 * self.beta / (n * D)))
         return dz.view(dq.shape)
 
-    def apply_ema(self, update_trackers: bool = True):
+    def apply_ema(self, update_trackers: bool = True, guarded: bool = False):
+        """guarded (a model whose optimizer skips non-finite steps): the update is skipped iff the summed statistics
+        m_sumT | n_sum hold a NaN or an inf: `stats_ok` is written from them on the device (vqa_grad_finite) and
+        the guarded entry point leaves E, ET, m_t, N_t, calls, the metrics, |e|^2 and the bf16 planes untouched on
+        a 0. The rule is the codebook's own: it is not trained by gradients, so it does not wait for theirs."""
+        ok = None
+        if guarded:
+            ok = self.stats_ok
+            K, D = self.num_embeddings, self.embedding_dim
+            V.grad_finite(self.stats[:K * D + K], ok)
         # the new codebook's |e|^2 and bf16 planes (the next argmin's inputs) come out of the same launch
         V.vq_ema_apply(self.embeddings, self.ET, self.m_t, self.N_t, self.m_sumT, self.n_sum, self.RT, self._g,
                        self._omg, float(self.codebook_usage_threshold), self.vq_metrics, self.calls,
-                       esq=self.e_sqnorm, E3=self.E3)
-        if update_trackers:
+                       esq=self.e_sqnorm, E3=self.E3, ok=ok)
+        if update_trackers and guarded:
+            for t, v in zip(self.metrics, self.vq_metrics):
+                t.update_state_if(v, ok)
+        elif update_trackers:
             self.batch_usage_tracker.update_state(self.vq_metrics[0])
             self.usage_tracker.update_state(self.vq_metrics[1])
             self.entropy_tracker.update_state(self.vq_metrics[2])

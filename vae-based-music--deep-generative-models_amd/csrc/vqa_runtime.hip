@@ -8,6 +8,9 @@
 //                    (a deterministic norm pass, then the same update on the clipped gradient).
 //   vqa_adam_keras_ema / vqa_adam_keras_clipped_ema : the same updates with an exponential moving average of the
 //                    weights kept in the same pass; vqa_swap_f32 exchanges the weights and their average.
+//   vqa_grad_finite / vqa_adam_keras_guarded / vqa_counter_add_if / vqa_step_metrics_if : a step whose aggregated
+//                    gradient holds a NaN or an inf is not applied (Keras' LossScaleOptimizer rule), decided on the
+//                    device so a captured step replays the decision.
 #include "vqa_launch.h"
 #include <stdarg.h>
 #include <stdio.h>
@@ -520,6 +523,74 @@ __global__ __launch_bounds__(256) void adam_clip_ema_kernel(float* w, const floa
   adam_clip_body<true>(w, g, m, v, n, ad, gs, seg_start, block_seg, nseg, modes, cv, cn, seg_norm, stats, ema, &av);
 }
 
+// ---- skipping non-finite steps ---------------------------------------------------------------------------
+// ok[0] = 1 iff every float of g is finite (the exponent field is not all ones: any finite value, denormals and
+// -0.0 pass; NaN and +-inf do not). flag_set_kernel writes the 1, grad_finite_kernel clears it with an integer
+// atomic AND: nothing is kept between calls and the result does not depend on the order of the workgroups.
+// One grid-stride loop over units: first the n4 groups of four behind the `head` floats that precede the first
+// 16-byte boundary (16-byte loads), then those head floats and the tail behind the last whole group one by one.
+__global__ void flag_set_kernel(int* ok) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) ok[0] = 1;
+}
+
+__device__ __forceinline__ bool finite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+__global__ __launch_bounds__(256) void grad_finite_kernel(const float* g, long long n, long long head, long long n4,
+                                                         int* ok) {
+  const long long tail0 = head + 4 * n4;           // the first element behind the groups of four
+  const long long units = n4 + head + (n - tail0);  // groups, then the head's and the tail's single floats
+  const f32x4* q = (const f32x4*)(g + head);
+  bool fin = true;
+  for (long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x; u < units;
+       u += (long long)gridDim.x * blockDim.x) {
+    if (u < n4) {
+      const f32x4 x = q[u];
+      fin = fin && finite_f32(x[0]) && finite_f32(x[1]) && finite_f32(x[2]) && finite_f32(x[3]);
+    } else {
+      const long long j = u - n4;
+      fin = fin && finite_f32(g[j < head ? j : tail0 + (j - head)]);
+    }
+  }
+  if (__any(!fin) && (threadIdx.x & 63) == 0) atomicAnd(ok, 0);
+}
+
+// The guard of one update launch: is the step applied (ok[0] == 1)? The launch's first thread keeps the counters,
+// skips[0] = steps skipped in all, skips[1] = steps skipped in a row. No other thread touches them.
+__device__ __forceinline__ bool guard_step(const int* ok, int64_t* skips) {
+  const bool go = ok[0] == 1;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (go) {
+      skips[1] = 0;
+    } else {
+      skips[0] += 1;
+      skips[1] += 1;
+    }
+  }
+  return go;
+}
+
+// The four updates above behind the guard, as one kernel: adam_clip_body with modes == 0 is adam_kernel's update
+// (u = grad_scale * g; the tables are not read), with EMA the average goes along. A skipped step returns before
+// any load or store of w, m, v and ema.
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_guarded_kernel(float* w, const float* g, float* m, float* v, float* ema,
+                                                          long long n, const int64_t* step, float lr0,
+                                                          const float* lr_dev, float b1, float b2, float eps, float gs,
+                                                          const int64_t* seg_start, const int* block_seg, int nseg,
+                                                          int modes, float cv, float cn, const float* seg_norm,
+                                                          const float* stats, float decay, long long start,
+                                                          int dynamic, const int* ok, int64_t* skips) {
+  if (!guard_step(ok, skips)) return;
+  const AdamStep ad(step, lr0, lr_dev, b1, b2, eps);
+  if (EMA) {
+    const EmaStep av(step, decay, start, dynamic);
+    adam_clip_body<true>(w, g, m, v, n, ad, gs, seg_start, block_seg, nseg, modes, cv, cn, seg_norm, stats, ema, &av);
+  } else {
+    adam_clip_body<false>(w, g, m, v, n, ad, gs, seg_start, block_seg, nseg, modes, cv, cn, seg_norm, stats, nullptr,
+                          nullptr);
+  }
+}
+
 // keras LearningRateSchedule evaluated on the device at the optimizer's step counter (OptimizerV2._decayed_lr
 // calls the schedule with float(iterations), the count BEFORE this step's increment), so a captured step replays
 // with the right rate. Host-precomputed float32 constants keep the arithmetic TF's:
@@ -545,14 +616,18 @@ __global__ void counter_add_kernel(int64_t* c, int64_t delta) {
   if (threadIdx.x == 0 && blockIdx.x == 0) c[0] += delta;
 }
 
+// the step counter of a guarded step: it advances only when the step was applied
+__global__ void counter_add_if_kernel(int64_t* c, int64_t delta, const int* ok) {
+  if (threadIdx.x == 0 && blockIdx.x == 0 && ok[0] == 1) c[0] += delta;
+}
+
 // The step's metric trackers (vqvae.py:262-304 update_metrics, VectorQuantizer.py:149-159) as one launch:
 // macc rows [loss, recon, vqvae, spectral] then per level [level, recon, vq, spectral, batch_usage, usage,
 // entropy], each (total, count). loss_slots = per level (recon, commit, spectral) sums over ranks, scaled by
 // 1/world; the Python sums of the reference are left folds: level = (recon + commit) + spectral,
 // total = ((0 + level_0) + level_1) + ...
-__global__ void step_metrics_kernel(const float* loss_slots, const float* vqm, float* macc, int levels,
-                                    float scale) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void step_metrics_body(const float* loss_slots, const float* vqm, float* macc, int levels,
+                                                  float scale) {
   float tot = 0.f, tr = 0.f, tc = 0.f, ts = 0.f;
   for (int l = 0; l < levels; ++l) {
     const float r = loss_slots[3 * l] * scale, c = loss_slots[3 * l + 1] * scale, sp = loss_slots[3 * l + 2] * scale;
@@ -573,6 +648,19 @@ __global__ void step_metrics_kernel(const float* loss_slots, const float* vqm, f
     macc[2 * i] += g[i];
     macc[2 * i + 1] += 1.f;
   }
+}
+
+__global__ void step_metrics_kernel(const float* loss_slots, const float* vqm, float* macc, int levels,
+                                    float scale) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  step_metrics_body(loss_slots, vqm, macc, levels, scale);
+}
+
+// a skipped step (ok[0] != 1) leaves every tracker row as it is, total and count
+__global__ void step_metrics_if_kernel(const float* loss_slots, const float* vqm, float* macc, int levels,
+                                       float scale, const int* ok) {
+  if (threadIdx.x != 0 || blockIdx.x != 0 || ok[0] != 1) return;
+  step_metrics_body(loss_slots, vqm, macc, levels, scale);
 }
 
 // ---- on-device synthetic waveform feed (replaces the host-side chunk feed of
@@ -793,6 +881,71 @@ extern "C" int vqa_adam_keras_clipped_ema(float* w, const float* g, float* m, fl
   return VQA_OK;
 }
 
+// ---- skipping non-finite steps
+extern "C" int vqa_grad_finite(const float* g, int64_t n, int32_t* ok, vqa_stream_t stream) {
+  VQA_ARG(n > 0, "grad_finite: n must be > 0 (got %lld)", (long long)n);
+  VQA_ARG(g && ok, "grad_finite: null pointer");
+  VQA_ARG((uintptr_t)g % 4 == 0 && (uintptr_t)ok % 4 == 0, "grad_finite: g and ok must be 4-byte aligned");
+  const long long head = std::min<long long>((long long)((16 - (uintptr_t)g % 16) % 16 / 4), n);
+  const long long n4 = (n - head) / 4, units = n4 + (n - 4 * n4);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(flag_set_kernel, dim3(1), dim3(64), 0, s, ok);
+  VQA_LAUNCHED("flag_set_kernel");
+  hipLaunchKernelGGL(grad_finite_kernel, dim3(blocks_for(units, VQA_FINITE_MAX_BLOCKS)), dim3(256), 0, s, g,
+                     (long long)n, head, n4, ok);
+  VQA_LAUNCHED("grad_finite_kernel");
+  return VQA_OK;
+}
+
+// do the 8 bytes at `a` and the `nb` int64 at `b` share a byte?
+static bool overlap_i64(const int64_t* a, const int64_t* b, int nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y ? y - x < sizeof(int64_t) : x - y < (uintptr_t)nb * sizeof(int64_t);
+}
+
+extern "C" int vqa_adam_keras_guarded(float* w, const float* g, float* m, float* v, int64_t n, const int64_t* step,
+                                      float lr, const float* lr_dev, float beta1, float beta2, float eps,
+                                      float grad_scale, const int64_t* seg_start, const int32_t* block_seg, int nseg,
+                                      int modes, float clipvalue, float clipnorm, float global_clipnorm,
+                                      const float* seg_norm, const float* stats, float* ema, float average_decay,
+                                      int64_t start_step, int dynamic, const int32_t* ok, int64_t* skip_counters,
+                                      vqa_stream_t stream) {
+  const char* what = "adam_guarded";
+  VQA_ARG(n > 0, "%s: n must be > 0 (got %lld)", what, (long long)n);
+  VQA_ARG(ok, "%s: null ok flag", what);
+  VQA_ARG(skip_counters, "%s: null skip counters", what);
+  VQA_ARG(!step || !overlap_i64(step, skip_counters, 2), "%s: the skip counters must not alias the step counter",
+          what);
+  int rc = VQA_OK;
+  if (modes != 0) {
+    rc = clip_check(what, n, seg_start, block_seg, nseg, modes, clipvalue, clipnorm, global_clipnorm);
+    if (rc != VQA_OK) return rc;
+    VQA_ARG(seg_norm && stats, "%s: null pointer (seg_norm, stats)", what);
+  } else {
+    VQA_ARG(clip_blocks(n) < (1LL << 31), "%s: n %lld too large", what, (long long)n);
+  }
+  if (ema) {
+    rc = ema_check(what, w, ema, n, average_decay, start_step, dynamic);
+    if (rc != VQA_OK) return rc;
+  }
+  VQA_ARG(w && g && m && v && step, "%s: null pointer", what);
+  VQA_ARG(((uintptr_t)w | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) % 16 == 0,
+          "%s: w, g, m, v and the average must be 16-byte aligned", what);
+  const dim3 grid((int)clip_blocks(n));
+  hipStream_t s = (hipStream_t)stream;
+  if (ema) {
+    hipLaunchKernelGGL(adam_guarded_kernel<true>, grid, dim3(256), 0, s, w, g, m, v, ema, (long long)n, step, lr,
+                       lr_dev, beta1, beta2, eps, grad_scale, seg_start, block_seg, nseg, modes, clipvalue, clipnorm,
+                       seg_norm, stats, average_decay, (long long)start_step, dynamic, ok, skip_counters);
+  } else {
+    hipLaunchKernelGGL(adam_guarded_kernel<false>, grid, dim3(256), 0, s, w, g, m, v, ema, (long long)n, step, lr,
+                       lr_dev, beta1, beta2, eps, grad_scale, seg_start, block_seg, nseg, modes, clipvalue, clipnorm,
+                       seg_norm, stats, 0.f, 0LL, 0, ok, skip_counters);
+  }
+  VQA_LAUNCHED("adam_guarded_kernel");
+  return VQA_OK;
+}
+
 extern "C" int vqa_lr_schedule(const int64_t* step, float* lr, int kind, float p0, float p1, float p2, float p3,
                                vqa_stream_t stream) {
   VQA_ARG(step && lr && kind >= 0 && kind <= 2, "lr_schedule: bad arguments (kind %d)", kind);
@@ -809,12 +962,30 @@ extern "C" int vqa_counter_add(int64_t* counter, int64_t delta, vqa_stream_t str
   return VQA_OK;
 }
 
+extern "C" int vqa_counter_add_if(int64_t* counter, int64_t delta, const int32_t* ok, vqa_stream_t stream) {
+  VQA_ARG(counter, "counter_add_if: null pointer");
+  VQA_ARG(ok, "counter_add_if: null ok flag");
+  hipLaunchKernelGGL(counter_add_if_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, counter, delta, ok);
+  VQA_LAUNCHED("counter_add_if_kernel");
+  return VQA_OK;
+}
+
 extern "C" int vqa_step_metrics(const float* loss_slots, const float* vq_metrics, float* macc, int levels, float scale,
                                 vqa_stream_t stream) {
   VQA_ARG(loss_slots && vq_metrics && macc && levels > 0, "step_metrics: bad arguments");
   hipLaunchKernelGGL(step_metrics_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_slots, vq_metrics, macc,
                      levels, scale);
   VQA_LAUNCHED("step_metrics_kernel");
+  return VQA_OK;
+}
+
+extern "C" int vqa_step_metrics_if(const float* loss_slots, const float* vq_metrics, float* macc, int levels,
+                                   float scale, const int32_t* ok, vqa_stream_t stream) {
+  VQA_ARG(loss_slots && vq_metrics && macc && levels > 0, "step_metrics_if: bad arguments");
+  VQA_ARG(ok, "step_metrics_if: null ok flag");
+  hipLaunchKernelGGL(step_metrics_if_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_slots, vq_metrics, macc,
+                     levels, scale, ok);
+  VQA_LAUNCHED("step_metrics_if_kernel");
   return VQA_OK;
 }
 

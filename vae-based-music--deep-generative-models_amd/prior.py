@@ -38,8 +38,8 @@ from vqa_layers import CKPT_VERSION, ParamStore, checkpoint_layout
 from vqa_metrics import Mean
 from vqa_module import keras_evaluate, keras_fit_feed
 from vqa_optim import Adam
-from vqa_train import (CapturedStep, adam_from_checkpoint, adam_state, averaged_weights, refuse_averaged,
-                       set_adam_state)
+from vqa_train import (CapturedStep, adam_from_checkpoint, adam_state, averaged_weights, check_skip_limit,
+                       refuse_averaged, set_adam_state)
 
 
 def create_look_ahead_mask(q_len, k_len):
@@ -798,7 +798,10 @@ class Prior:
 
     def results(self):
         loss = self.train_loss_tracker.result()
-        return {"loss": loss, "perplexity(per word)": torch.exp(loss), "accuracy": self.train_accuracy_tracker.result()}
+        out = {"loss": loss, "perplexity(per word)": torch.exp(loss), "accuracy": self.train_accuracy_tracker.result()}
+        if self.optimizer.skip_nonfinite:
+            out["skipped_steps"] = self.optimizer.skip_stats()["skipped_steps"]
+        return out
 
     # -------------------------------------------------------------- the step
     def _label_embed(self, y):
@@ -890,14 +893,24 @@ class Prior:
         vqa_dp.exchange(self.bucket, self.process_group)
 
     def _apply(self):
-        """Keras Adam on the (rank-mean) gradients, then the trackers on the global means."""
+        """Keras Adam on the (rank-mean) gradients, then the trackers on the global means. With an optimizer that
+        skips non-finite steps the trackers follow its flag: a skipped step leaves their totals and counts as they
+        are."""
         w = vqa_dp.world_size(self.process_group)
         self.optimizer.apply(self.prior.store, grad_scale=1.0 / w)
+        if self.optimizer.skip_nonfinite:
+            ok = self.optimizer.step_ok
+            self.train_loss_tracker.update_state_if(self._scalars[0] / w, ok)
+            self.train_accuracy_tracker.update_state_if(self._scalars[1] / w, ok)
+            return
         self.train_loss_tracker.update_state(self._scalars[0] / w)
         self.train_accuracy_tracker.update_state(self._scalars[1] / w)
 
     def train_step(self, x, teacher_force_rate=0.2, tf_mask=None):
-        """prior.py:241-335. tf_mask (N, T) bool overrides the random teacher-forcing draw (parity tests)."""
+        """prior.py:241-335. tf_mask (N, T) bool overrides the random teacher-forcing draw (parity tests).
+        With an optimizer that skips non-finite steps, the host count `_step` (and a feed's step counter) counts
+        attempted steps: a skipped batch is dropped, not retried. The dropout and teacher-forcing draws are keyed by
+        the optimizer's device step count, which a skipped step leaves where it was."""
         refuse_averaged(self, "train_step")
         # the captured graph bakes in its teacher-forcing rate: another rate (e.g. a schedule) runs eagerly
         replayable = (self._captured is not None and tf_mask is None
@@ -1024,15 +1037,20 @@ class Prior:
         self._captured = step
         self._graph_rate = float(teacher_force_rate)
 
-    def fit(self, x, epochs=1, teacher_force_rate=0.2, verbose=0):
+    def fit(self, x, epochs=1, teacher_force_rate=0.2, verbose=0, max_consecutive_skips=None):
         """Minimal keras fit over a code_feed.CodeFeed: the trackers reset per epoch (keras semantics), an epoch is
         the feed's steps_per_epoch steps (graph replays once the step is captured with that feed); batch size,
-        shuffling and seed are the feed's. Returns the history of epoch-end results."""
+        shuffling and seed are the feed's. Returns the history of epoch-end results.
+        max_consecutive_skips (an optimizer with skip_nonfinite only, else ValueError before any launch): the count
+        of steps skipped in a row is read once at each epoch end; at the limit a FloatingPointError names the epoch
+        and both counts. A skipped batch is dropped, not retried."""
         refuse_averaged(self, "fit")
+        check_skip_limit(self.optimizer, max_consecutive_skips)
         if not isinstance(x, CodeFeed):
             raise ValueError("Prior.fit trains from a code_feed.CodeFeed")
         self._check_feed(x)
-        return keras_fit_feed(self, x, epochs, verbose, teacher_force_rate=teacher_force_rate)
+        return keras_fit_feed(self, x, epochs, verbose, max_consecutive_skips=max_consecutive_skips,
+                              teacher_force_rate=teacher_force_rate)
 
     # -------------------------------------------------------------- checkpoint
     def save(self, path: str):

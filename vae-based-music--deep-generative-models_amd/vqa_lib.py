@@ -50,6 +50,8 @@ EXPORTED = [
     "vqa_attn_weights_elems", "vqa_attn_weights",
     "vqa_grad_norm", "vqa_grad_norm_workspace", "vqa_adam_keras_clipped",
     "vqa_adam_keras_ema", "vqa_adam_keras_clipped_ema", "vqa_swap_f32",
+    "vqa_grad_finite", "vqa_adam_keras_guarded", "vqa_counter_add_if", "vqa_step_metrics_if",
+    "vqa_vq_ema_apply_guarded",
 ]
 
 
@@ -102,6 +104,12 @@ _SIGS = {
     "vqa_adam_keras_clipped_ema": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _F, _F, _F, _F, _P, _P, _I, _I, _F, _F, _F, _P,
                                         _P, _P, _F, _L, _I, _P]),
     "vqa_swap_f32": (_I, [_P, _P, _L, _P]),
+    "vqa_grad_finite": (_I, [_P, _L, _P, _P]),
+    "vqa_adam_keras_guarded": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _F, _F, _F, _F, _P, _P, _I, _I, _F, _F, _F, _P,
+                                    _P, _P, _F, _L, _I, _P, _P, _P]),
+    "vqa_counter_add_if": (_I, [_P, _L, _P, _P]),
+    "vqa_step_metrics_if": (_I, [_P, _P, _P, _I, _F, _P, _P]),
+    "vqa_vq_ema_apply_guarded": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P, _I, _I, _P, _P]),
     "vqa_lr_schedule": (_I, [_P, _P, _I, _F, _F, _F, _F, _P]),
     "vqa_counter_add": (_I, [_P, _L, _P]),
     "vqa_step_metrics": (_I, [_P, _P, _P, _I, _F, _P]),
@@ -506,11 +514,18 @@ def vq_reset_rows(z, RT, row_offset, N_global, seed, counter, level):
                                    dtype_code(z.dtype), stream()), "vqa_vq_reset_rows")
 
 
-def vq_ema_apply(E, ET, m_t, N_t, m_sumT, n_sum, RT, gamma, omg, thresh, metrics, counter, esq=None, E3=None):
-    """EMA + dead-code reset; with esq / E3 also |e|^2 and the bf16 planes of the new codebook (same pass)."""
+def vq_ema_apply(E, ET, m_t, N_t, m_sumT, n_sum, RT, gamma, omg, thresh, metrics, counter, esq=None, E3=None,
+                 ok=None):
+    """EMA + dead-code reset; with esq / E3 also |e|^2 and the bf16 planes of the new codebook (same pass). With
+    `ok` (an int32 device flag, grad_finite's) the guarded form: nothing is written unless ok[0] == 1."""
     D, K = E.shape
     if E3 is not None and (E3.dtype != torch.bfloat16 or tuple(E3.shape) != (K, 3, D)):
         raise VQAError(f"vq_ema_apply: E3 must be ({K}, 3, {D}) bf16")
+    if ok is not None:
+        _check(lib().vqa_vq_ema_apply_guarded(ptr(E), ptr(ET), ptr(m_t), ptr(N_t), ptr(m_sumT), ptr(n_sum), ptr(RT),
+                                              gamma, omg, thresh, ptr(metrics), ptr(counter), ptr(esq), ptr(E3), D, K,
+                                              _flag(ok), stream()), "vqa_vq_ema_apply_guarded")
+        return
     _check(lib().vqa_vq_ema_apply_derived(ptr(E), ptr(ET), ptr(m_t), ptr(N_t), ptr(m_sumT), ptr(n_sum), ptr(RT), gamma,
                                           omg, thresh, ptr(metrics), ptr(counter), ptr(esq), ptr(E3), D, K, stream()),
            "vqa_vq_ema_apply_derived")
@@ -581,6 +596,40 @@ def swap_f32(a, b):
     _check(lib().vqa_swap_f32(ptr(a), ptr(b), a.numel(), stream()), "vqa_swap_f32")
 
 
+FINITE_MAX_BLOCKS = 4096  # VQA_FINITE_MAX_BLOCKS: vqa_grad_finite's grid cap (workgroups of 256)
+
+
+def _flag(ok):
+    if ok.dtype != torch.int32:
+        raise VQAError("the step guard's flag is an int32 device tensor")
+    return ptr(ok)
+
+
+def grad_finite(g, ok):
+    """ok[0] = 1 if every float of g is finite, else 0 (vqa_grad_finite; ok: int32 device tensor)."""
+    if g.dtype != torch.float32:
+        raise VQAError("grad_finite: a float32 buffer")
+    flag = _flag(ok)
+    _check(lib().vqa_grad_finite(ptr(g), g.numel(), flag, stream()), "vqa_grad_finite")
+
+
+def adam_keras_guarded(w, g, m, v, step, lr, beta1, beta2, eps, grad_scale, ok, skip_counters, clip=None, ema=None,
+                       lr_dev=None):
+    """The Adam update behind grad_finite's flag (vqa_adam_keras_guarded). clip: None or (seg_start, block_seg,
+    modes, clipvalue, clipnorm, global_clipnorm, seg_norm, stats); ema: None or (average, average_decay, start_step,
+    dynamic). skip_counters: int64[2] device tensor (skipped in all, skipped in a row)."""
+    seg_start, block_seg, modes, cv, cn, gcn, seg_norm, stats = clip or (None, None, 0, 0.0, 0.0, 0.0, None, None)
+    average, decay, start, dynamic = ema or (None, 0.0, 0, False)
+    if skip_counters.dtype != torch.int64 or skip_counters.numel() != 2:
+        raise VQAError("adam_keras_guarded: skip_counters is an int64 device tensor of 2")
+    _check(lib().vqa_adam_keras_guarded(ptr(w), ptr(g), ptr(m), ptr(v), w.numel(), ptr(step), float(lr), ptr(lr_dev),
+                                        beta1, beta2, eps, grad_scale, ptr(seg_start), ptr(block_seg),
+                                        0 if seg_start is None else seg_start.numel(), int(modes), cv, cn, gcn,
+                                        ptr(seg_norm), ptr(stats), ptr(average), float(decay), int(start),
+                                        int(bool(dynamic)), _flag(ok), ptr(skip_counters), stream()),
+           "vqa_adam_keras_guarded")
+
+
 def lr_schedule(step, lr_out, kind, p):
     p = list(p) + [0.0] * (4 - len(p))
     _check(lib().vqa_lr_schedule(ptr(step), ptr(lr_out), int(kind), *[float(v) for v in p[:4]], stream()),
@@ -590,6 +639,11 @@ def lr_schedule(step, lr_out, kind, p):
 def step_metrics(loss_slots, vq_metrics, macc, levels, scale):
     _check(lib().vqa_step_metrics(ptr(loss_slots), ptr(vq_metrics), ptr(macc), levels, scale, stream()),
            "vqa_step_metrics")
+
+
+def step_metrics_if(loss_slots, vq_metrics, macc, levels, scale, ok):
+    _check(lib().vqa_step_metrics_if(ptr(loss_slots), ptr(vq_metrics), ptr(macc), levels, scale, _flag(ok), stream()),
+           "vqa_step_metrics_if")
 
 
 def synthetic_batch(x, seed, rank=0, sample_rate=44100.0):
@@ -639,6 +693,11 @@ def layernorm_bwd(x, dy, gamma, dx, dgamma, dbeta, eps, deferred=None):
 
 def counter_add(counter, delta=1):
     _check(lib().vqa_counter_add(ptr(counter), delta, stream()), "vqa_counter_add")
+
+
+def counter_add_if(counter, ok, delta=1):
+    """counter += delta if ok[0] == 1 (vqa_counter_add_if)."""
+    _check(lib().vqa_counter_add_if(ptr(counter), delta, _flag(ok), stream()), "vqa_counter_add_if")
 
 
 PCM_I16, PCM_F32 = 0, 1  # VQA_PCM_*

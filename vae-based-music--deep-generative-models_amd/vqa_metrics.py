@@ -19,6 +19,13 @@ class Mean:
         self._acc[0].add_(value.reshape(()).to(torch.float32))
         self._acc[1].add_(1.0)
 
+    def update_state_if(self, value: torch.Tensor, ok: torch.Tensor):
+        """update_state(value) where the device flag `ok` (the optimizer's step guard) is 1; otherwise total and count
+        keep their bits. Device ops only, so a captured step replays the choice."""
+        one = torch.ones((), dtype=torch.float32, device=self._acc.device)
+        new = self._acc + torch.stack([value.reshape(()).to(torch.float32), one])
+        self._acc.copy_(torch.where(ok.reshape(()) == 1, new, self._acc))
+
     def result(self) -> torch.Tensor:
         return self._acc[0] / self._acc[1].clamp(min=1.0)
 

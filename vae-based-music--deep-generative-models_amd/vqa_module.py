@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from vqa_layers import ParamStore
+from vqa_train import check_skip_limit, raise_on_skips
 
 
 class Layer:
@@ -58,9 +59,14 @@ def _is_array(a) -> bool:
     return isinstance(a, (torch.Tensor, np.ndarray))
 
 
-def keras_fit_feed(model, feed, epochs=1, verbose=0, **train_step_kwargs):
+def keras_fit_feed(model, feed, epochs=1, verbose=0, max_consecutive_skips=None, **train_step_kwargs):
     """keras Model.fit over a device feed (AudioFeed, CodeFeed): the metrics reset per epoch, an epoch is the feed's
-    steps_per_epoch calls of model.train_step(feed, **train_step_kwargs); returns the epoch-end results as floats."""
+    steps_per_epoch calls of model.train_step(feed, **train_step_kwargs); returns the epoch-end results as floats.
+    max_consecutive_skips: with an optimizer that skips non-finite steps (ValueError otherwise, before any launch),
+    the count of steps skipped in a row is read once at each epoch end and a FloatingPointError raised when it has
+    reached the limit; no read is made inside an epoch. The feed's step counter counts attempted steps: a skipped
+    batch is dropped, not drawn again."""
+    check_skip_limit(model.optimizer, max_consecutive_skips)
     hist = []
     for ep in range(epochs):
         model.reset_metrics()
@@ -69,6 +75,7 @@ def keras_fit_feed(model, feed, epochs=1, verbose=0, **train_step_kwargs):
         hist.append({k: float(v) for k, v in model.results().items()})
         if verbose:
             print(f"epoch {ep + 1}/{epochs}", hist[-1])
+        raise_on_skips(model.optimizer, max_consecutive_skips, ep)
     return hist
 
 

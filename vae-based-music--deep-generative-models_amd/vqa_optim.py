@@ -21,6 +21,15 @@ rule), keyed by the same device step count as a learning-rate schedule, so a cap
 `average_start_step` and `dynamic_average_decay` are tfa's start_step and dynamic_decay. assign_average_vars and
 swap_weights carry tfa's names; swap_weights exchanges contents exactly (vqa_swap_f32). The three settings are
 configuration like the thresholds; the average itself is state and travels in checkpoints.
+
+Skipping non-finite steps is Keras' LossScaleOptimizer rule without the loss scale: with `skip_nonfinite=True` a step
+whose aggregated gradient holds a NaN or an inf is not applied. vqa_grad_finite writes a device flag from the gradient
+(after the data-parallel exchange, so every rank reads the same bits and decides alike), the update and the increment
+of `iterations` run behind it (vqa_adam_keras_guarded, vqa_counter_add_if), and two device counters keep the skipped
+steps in all and in a row. A skipped step writes no byte of the weights, the moments or the average and leaves
+`iterations`, hence the bias correction, a schedule's rate and the average's start step and dynamic decay, where they
+were. Nothing is read back; a captured step replays the decision. The setting is configuration; the two counters are
+state and travel in checkpoints.
 """
 from __future__ import annotations
 
@@ -34,6 +43,8 @@ from schedules import LearningRateSchedule
 
 # Adam.grad_stats() keys, in the order of vqa_grad_norm's `stats`
 GRAD_STATS = ("global_norm", "clipped_global_norm", "global_scale", "clipnorm_variables", "clipvalue_elements")
+# Adam.skip_stats() keys
+SKIP_STATS = ("skipped_steps", "consecutive_skipped", "last_step_ok")
 
 
 def _threshold(name, value):
@@ -82,7 +93,7 @@ def clip_tables(offsets, size: int):
 class Adam:
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, *, clipvalue=None,
                  clipnorm=None, global_clipnorm=None, average_decay=None, average_start_step=0,
-                 dynamic_average_decay=False, **kwargs):
+                 dynamic_average_decay=False, skip_nonfinite=False, **kwargs):
         if callable(learning_rate) and not isinstance(learning_rate, LearningRateSchedule):
             # a host callable cannot be evaluated inside a replayed hipGraph
             raise TypeError("learning_rate: a float or a schedules.LearningRateSchedule (device-evaluated)")
@@ -95,11 +106,16 @@ class Adam:
         self.global_clipnorm = _threshold("global_clipnorm", global_clipnorm)
         self.average_decay, self.average_start_step, self.dynamic_average_decay = _average_settings(
             average_decay, average_start_step, dynamic_average_decay)
+        if not isinstance(skip_nonfinite, (bool, np.bool_)):
+            raise ValueError(f"skip_nonfinite: True or False (got {skip_nonfinite!r})")
+        self.skip_nonfinite = bool(skip_nonfinite)
         self.iterations = None
         self.m = self.v = None
         self.average = None  # the weights' moving average, a flat buffer like store.flat (build)
         self._lr_dev = None
         self._clip = None  # device tables, norms, statistics and workspace of the clipped path (build)
+        self.step_ok = None  # the guard's flag (int32[1]) and counters (int64[2]: skipped in all, in a row) (build)
+        self.skipped = None
 
     @property
     def scheduled(self) -> bool:
@@ -122,6 +138,10 @@ class Adam:
         self._lr_dev = torch.zeros(1, dtype=torch.float32, device=dev) if self.scheduled else None
         # allocated once (a captured step keeps the pointer); starts as the weights, as tfa's slot does
         self.average = store.flat.detach().clone() if self.averaging else None
+        if self.skip_nonfinite:
+            # allocated once: a captured step keeps these pointers
+            self.step_ok = torch.ones(1, dtype=torch.int32, device=dev)
+            self.skipped = torch.zeros(2, dtype=torch.int64, device=dev)
         if self.clip_modes:
             # allocated once: a captured step keeps these pointers
             seg, block_seg = clip_tables(store.offsets, store.size)
@@ -152,9 +172,19 @@ class Adam:
             raise RuntimeError("variable_grad_norms: no clipping configured, or the optimizer is not built yet")
         return self._clip["seg_norm"]
 
+    def skip_stats(self):
+        """The step guard's state as 0-dim device tensors (views of the buffers the step writes; no host sync): the
+        steps skipped in all, the steps skipped in a row up to and including the last one (0 after an applied step),
+        and the last step's flag (1 applied, 0 skipped)."""
+        if self.skipped is None:
+            raise RuntimeError("skip_stats: skip_nonfinite is off, or the optimizer is not built yet")
+        return dict(zip(SKIP_STATS, (self.skipped[0], self.skipped[1], self.step_ok[0])))
+
     def apply(self, store, grad_scale: float = 1.0):
         if self.m is None:
             self.build(store)
+        if self.skip_nonfinite:
+            return self._apply_guarded(store, grad_scale)
         lr = 0.0
         if self.scheduled:
             kind, p = self.learning_rate.device_spec()
@@ -184,6 +214,30 @@ class Adam:
                                      self.epsilon, grad_scale, c["seg_start"], c["block_seg"], self.clip_modes, *thr,
                                      c["seg_norm"], c["stats"], lr_dev=self._lr_dev)
         V.counter_add(self.iterations, 1)
+
+    def _apply_guarded(self, store, grad_scale):
+        """apply() with skip_nonfinite: the flag from the aggregated gradient, then the same schedule, norm pass and
+        update behind it."""
+        g = store.grad[:store.size]
+        V.grad_finite(g, self.step_ok)
+        lr = 0.0
+        if self.scheduled:
+            kind, p = self.learning_rate.device_spec()
+            V.lr_schedule(self.iterations, self._lr_dev, kind, p)
+        else:
+            lr = self.learning_rate
+        clip = None
+        if self.clip_modes:
+            c = self._clip
+            thr = (self.clipvalue or 0.0, self.clipnorm or 0.0, self.global_clipnorm or 0.0)
+            V.grad_norm(g, c["seg_start"], c["block_seg"], grad_scale, self.clip_modes, *thr, c["seg_norm"],
+                        c["stats"], c["ws"])
+            clip = (c["seg_start"], c["block_seg"], self.clip_modes, *thr, c["seg_norm"], c["stats"])
+        ema = ((self.average, self.average_decay, self.average_start_step, self.dynamic_average_decay)
+               if self.averaging else None)
+        V.adam_keras_guarded(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2, self.epsilon,
+                             grad_scale, self.step_ok, self.skipped, clip=clip, ema=ema, lr_dev=self._lr_dev)
+        V.counter_add_if(self.iterations, self.step_ok)
 
     def _averaged(self, what, store):
         if not self.averaging:

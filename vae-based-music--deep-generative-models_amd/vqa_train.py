@@ -2,6 +2,7 @@
 checkpoint, and the context in which a model runs on the moving average of its weights. What differs between the models stays with them: their inputs and checks, and what surrounds a replay."""
 from __future__ import annotations
 
+import gc
 from contextlib import contextmanager
 
 import torch
@@ -38,22 +39,33 @@ class CapturedStep:
         """ONE graph (draw, compute, [exchange], update) when the step has no exchange (no data parallelism) or
         exchange_captured(), read after compute has run inside the capture, says the exchange runs on the device;
         otherwise TWO graphs (draw + compute, update) around the eager exchange."""
-        pool = torch.cuda.graph_pool_handle()
-        g1 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1, pool=pool, capture_error_mode="thread_local"):
-            self.draw()
-            self.compute()
-            captured = exchange_captured()
-            one_graph = captured or not vqa_dp.active(self.process_group)
-            if captured:
-                self.exchange()
-            if one_graph:
-                self.update()
-        g2 = None
-        if not one_graph:
-            g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g2, pool=pool, capture_error_mode="thread_local"):
-                self.update()
+        # A model and its CapturedStep refer to each other, so a dropped model (its hipGraphs, events and pool memory)
+        # is freed by the cycle collector only, whenever that next runs. Inside a capture that destroys GPU objects
+        # on the capturing thread, which the runtime answers with an abort: collect such garbage now, and keep the
+        # collector out of the capture (torch.cuda.graph no longer collects on entry).
+        gc.collect()
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            pool = torch.cuda.graph_pool_handle()
+            g1 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g1, pool=pool, capture_error_mode="thread_local"):
+                self.draw()
+                self.compute()
+                captured = exchange_captured()
+                one_graph = captured or not vqa_dp.active(self.process_group)
+                if captured:
+                    self.exchange()
+                if one_graph:
+                    self.update()
+            g2 = None
+            if not one_graph:
+                g2 = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g2, pool=pool, capture_error_mode="thread_local"):
+                    self.update()
+        finally:
+            if collecting:
+                gc.enable()
         self.graphs = (g1, g2)
         torch.cuda.synchronize(self.device)
 
@@ -96,13 +108,40 @@ def refuse_averaged(model, what):
         raise RuntimeError(f"{what}: not inside averaged_weights() (the weights hold their moving average)")
 
 
+def check_skip_limit(optimizer, max_consecutive_skips):
+    """fit's max_consecutive_skips, checked before anything is launched: None, or an integer >= 1 with an optimizer
+    that skips non-finite steps (vqa_optim.Adam(skip_nonfinite=True))."""
+    if max_consecutive_skips is None:
+        return
+    if (isinstance(max_consecutive_skips, bool) or not isinstance(max_consecutive_skips, int)
+            or max_consecutive_skips < 1):
+        raise ValueError(f"max_consecutive_skips: an integer >= 1 or None (got {max_consecutive_skips!r})")
+    if optimizer is None or not optimizer.skip_nonfinite:
+        raise ValueError("max_consecutive_skips needs an optimizer that skips non-finite steps "
+                         "(compile with vqa_optim.Adam(skip_nonfinite=True))")
+
+
+def raise_on_skips(optimizer, max_consecutive_skips, epoch):
+    """The epoch-end check of fit(max_consecutive_skips=...): the one read of the guard's counters."""
+    if max_consecutive_skips is None:
+        return
+    total, row = (int(c) for c in optimizer.skipped.tolist())
+    if row >= max_consecutive_skips:
+        raise FloatingPointError(f"epoch {epoch + 1}: the last {row} train steps in a row were skipped for a "
+                                 f"non-finite gradient (max_consecutive_skips={max_consecutive_skips}); "
+                                 f"{total} steps skipped in all")
+
+
 def adam_state(optimizer) -> dict:
-    """The optimizer's entries of a checkpoint: both moments (host copies), the step count and, when it keeps one,
-    the weights' moving average."""
+    """The optimizer's entries of a checkpoint: both moments (host copies), the step count, when it keeps one the
+    weights' moving average, and with skip_nonfinite the guard's two counters (adam_skipped: skipped in all, in a
+    row)."""
     sd = {"adam_m": optimizer.m.detach().cpu().clone(), "adam_v": optimizer.v.detach().cpu().clone(),
           "iterations": int(optimizer.iterations.item())}
     if optimizer.average is not None:
         sd["adam_ema"] = optimizer.average.detach().cpu().clone()
+    if optimizer.skipped is not None:
+        sd["adam_skipped"] = [int(c) for c in optimizer.skipped.tolist()]
     return sd
 
 
@@ -112,13 +151,16 @@ def adam_from_checkpoint(ck, store, layout, path) -> dict:
           "adam_v": store.from_layout(ck["adam_v"], layout, f"{path} (adam_v)"), "iterations": ck["iterations"]}
     if "adam_ema" in ck:
         sd["adam_ema"] = store.from_layout(ck["adam_ema"], layout, f"{path} (adam_ema)")
+    if "adam_skipped" in ck:
+        sd["adam_skipped"] = ck["adam_skipped"]
     return sd
 
 
 def set_adam_state(optimizer, sd, device, store=None):
     """`store` holds the weights already loaded: an averaging optimizer given a state without an average (a file
     written without averaging) starts its average from them. An average given to an optimizer that keeps none is
-    ignored."""
+    ignored. The skip counters (adam_skipped) load into a guarded optimizer, as zeros when the state has none (the
+    guard's flag starts as 1); an optimizer without the guard ignores them."""
     optimizer.m.copy_(sd["adam_m"].to(device))
     optimizer.v.copy_(sd["adam_v"].to(device))
     optimizer.iterations.fill_(int(sd["iterations"]))
@@ -127,3 +169,7 @@ def set_adam_state(optimizer, sd, device, store=None):
             optimizer.average.copy_(sd["adam_ema"].to(device))
         elif store is not None:
             optimizer.average.copy_(store.flat)
+    if optimizer.skipped is not None:
+        total, row = (int(c) for c in sd.get("adam_skipped", (0, 0)))
+        optimizer.skipped.copy_(torch.tensor([total, row], dtype=torch.int64))
+        optimizer.step_ok.fill_(0 if row else 1)

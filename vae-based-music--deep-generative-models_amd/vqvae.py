@@ -38,8 +38,8 @@ from vqa_layers import CKPT_VERSION, ParamStore, checkpoint_layout
 from vqa_metrics import SlotMean
 from vqa_module import keras_evaluate, keras_fit_feed
 from vqa_optim import Adam
-from vqa_train import (CapturedStep, adam_from_checkpoint, adam_state, averaged_weights, refuse_averaged,
-                       set_adam_state)
+from vqa_train import (CapturedStep, adam_from_checkpoint, adam_state, averaged_weights, check_skip_limit,
+                       raise_on_skips, refuse_averaged, set_adam_state)
 from VectorQuantizer import VectorQuantizer
 
 
@@ -382,7 +382,7 @@ class VQVAE:
             done = torch.cuda.Event()
             done.record(cur)
             self._exchange_events.append(done)  # alive until the next step's exchange (capture_end reads them)
-        self.vqs[l].apply_ema(update_trackers=False)
+        self.vqs[l].apply_ema(update_trackers=False, guarded=grads and self._guarded)
         return done
 
     def _level_streams(self):
@@ -415,7 +415,8 @@ class VQVAE:
             enc.backward(dz)
             self.store.deferred.flush()
         if ema:
-            vq.apply_ema(update_trackers=False)  # after every use of the old codebook in this level
+            # after every use of the old codebook in this level
+            vq.apply_ema(update_trackers=False, guarded=training_grads and self._guarded)
 
     def _update(self, apply_grads: bool):
         world = vqa_dp.world_size(self.process_group)
@@ -424,9 +425,14 @@ class VQVAE:
         if (vqa_dp.active(self.process_group) and not self._overlapped) or self._r3_layout:
             # else the levels' chains applied it (_compute)
             for vq in self.vqs:
-                vq.apply_ema(update_trackers=False)
+                vq.apply_ema(update_trackers=False, guarded=apply_grads and self._guarded)
         # update_metrics (vqvae.py:262-304) + the VQ trackers: one launch
-        V.step_metrics(self.loss_slots, self._vq_metrics, self._macc, self.levels, 1.0 / world)
+        if apply_grads and self._guarded:
+            # a skipped step leaves every tracker as it is (the optimizer's flag, written by the apply above)
+            V.step_metrics_if(self.loss_slots, self._vq_metrics, self._macc, self.levels, 1.0 / world,
+                              self.optimizer.step_ok)
+        else:
+            V.step_metrics(self.loss_slots, self._vq_metrics, self._macc, self.levels, 1.0 / world)
 
     def _exchange(self, grads: bool = True):
         """The step's one collective: all_reduce(SUM) of [grads | EMA sums | reset rows | losses]; without
@@ -466,9 +472,19 @@ class VQVAE:
         loss, _ = multispectral_loss_and_grad(SpectralTarget(x), r, need_grad=False)
         return loss.reshape(())
 
+    @property
+    def _guarded(self) -> bool:
+        """Does the optimizer skip non-finite steps (vqa_optim.Adam(skip_nonfinite=True))? Then a train step also
+        guards each level's codebook update (by that level's own statistics) and the trackers (by the gradient's
+        flag); test_step and evaluate are never guarded."""
+        return self.optimizer is not None and self.optimizer.skip_nonfinite
+
     def results(self) -> Dict[str, torch.Tensor]:
         res = self._macc[:, 0] / self._macc[:, 1].clamp(min=1.0)
-        return {n: res[i] for i, n in enumerate(self.metric_names)}
+        out = {n: res[i] for i, n in enumerate(self.metric_names)}
+        if self._guarded:
+            out["skipped_steps"] = self.optimizer.skip_stats()["skipped_steps"]
+        return out
 
     def train_step(self, data):
         """vqvae.py:111-146. Returns the running-mean metric dict (0-dim device tensors)."""
@@ -768,15 +784,21 @@ class VQVAE:
         return p.contiguous(), seam, int(fade_samples)
 
     # ------------------------------------------------------------------ training loop / state
-    def fit(self, x=None, y=None, batch_size=32, epochs=1, shuffle=True, seed=0, verbose=0):
+    def fit(self, x=None, y=None, batch_size=32, epochs=1, shuffle=True, seed=0, verbose=0,
+            max_consecutive_skips=None):
         """Minimal keras fit: `self.metrics` reset per epoch (keras semantics); returns the history of
         epoch-end results. With an audio_feed.AudioFeed as x an epoch is the feed's steps_per_epoch steps (graph
-        replays once the step is captured with that feed); batch size, shuffling and seed are the feed's."""
+        replays once the step is captured with that feed); batch size, shuffling and seed are the feed's.
+        max_consecutive_skips (an optimizer with skip_nonfinite only, else ValueError before any launch): at each
+        epoch end the optimizer's count of steps skipped in a row is read, once, and a FloatingPointError naming the
+        epoch and both counts is raised when it has reached the limit; nothing is read inside an epoch. A skipped
+        batch is dropped, not retried: the feed's step counter counts attempted steps."""
         refuse_averaged(self, "fit")
+        check_skip_limit(self.optimizer, max_consecutive_skips)
         if self.optimizer is None:
             self.compile()
         if isinstance(x, AudioFeed):
-            return keras_fit_feed(self, x, epochs, verbose)
+            return keras_fit_feed(self, x, epochs, verbose, max_consecutive_skips=max_consecutive_skips)
         xs = np.asarray(x, np.float32)
         n = xs.shape[0]
         rng = np.random.default_rng(seed)
@@ -788,6 +810,7 @@ class VQVAE:
                 self.train_step(xs[order[i:i + batch_size]])
             res = {k: float(v) for k, v in self.results().items()}
             hist.append(res)
+            raise_on_skips(self.optimizer, max_consecutive_skips, ep)
             if verbose:
                 print(f"epoch {ep + 1}/{epochs}", res)
         return hist
@@ -831,7 +854,7 @@ class VQVAE:
                           "latent_dim": self.latent_dim, "num_embeddings": self.num_embeddings,
                           "down_depth": list(self.down_depth), "strides": list(self.strides)},
                "weights": sd["weights"]}
-        for k in ("adam_m", "adam_v", "adam_ema", "iterations"):
+        for k in ("adam_m", "adam_v", "adam_ema", "adam_skipped", "iterations"):
             if k in sd:
                 out[k] = sd[k]
         for l, st in enumerate(sd["vq"]):
