@@ -1,4 +1,5 @@
-"""Plain Adam (vqa_adam_keras, vqa_runtime.hip adam_kernel) on its own: TF ApplyAdam over a flat fp32 buffer,
+"""Plain Adam (vqa_adam_keras, vqa_optim.hip adam_stride_kernel<false>) on its own: TF ApplyAdam over a flat fp32
+buffer,
     m += (g gs - m)(1 - b1);  v += ((g gs)^2 - v)(1 - b2);  w -= (m alpha) / (sqrt(v) + eps),
     alpha = lr sqrt(1 - b2^t) / (1 - b1^t), t = step + 1 read from the device.
 

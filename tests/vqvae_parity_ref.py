@@ -118,7 +118,7 @@ def mse_grad64(x, r, extra=None):
     return g + extra.double() if extra is not None else g
 
 
-# ---- Adam (vqa_runtime.hip adam_kernel)
+# ---- Adam (vqa_optim.hip AdamStep)
 def adam_mv(g, m, v, b1, b2, gs):
     """m += (g gs - m)(1 - b1), v += ((g gs)^2 - v)(1 - b2), every constant and operation in fp32."""
     gi = g * f32(gs)

@@ -5,7 +5,7 @@
 cfg2: the benched VQ-VAE's store (968,835 parameters). cfg4: the config-4 prior's (SMALL_PRIOR, ctx 8192). The
 gradient is a fixed normal draw; each variant runs `steps` applies after 3 warm-up ones and prints the mean time
 per apply (device events). Run it under `rocprofv3 --kernel-trace --stats` for the per-kernel times
-(adam_kernel, grad_norm_*_kernel, adam_clip_kernel).
+(adam_stride_kernel, grad_norm_*_kernel, adam_blocks_kernel).
 """
 import os
 import sys

@@ -5,8 +5,8 @@
 cfg2: the benched VQ-VAE's store (968,835 parameters). cfg4: the config-4 prior's (SMALL_PRIOR, ctx 8192). Three
 variants, in this one process and on the same buffers (weights, gradient, moments; the weights are restored before
 each variant):
-  plain     Adam.apply without an average (adam_kernel + the step counter's increment)
-  fused     Adam.apply with average_decay (adam_ema_kernel + the increment): the average in the Adam launch
+  plain     Adam.apply without an average (adam_stride_kernel<false> + the step counter's increment)
+  fused     Adam.apply with average_decay (adam_stride_kernel<true> + the increment): the average in the Adam launch
   unfused   the plain apply followed by a separate averaging pass written with torch ops on the flat buffers,
             a.sub_((a - w) * (1 - d)): what user code outside the library would run
 Every variant is warmed up, then timed `repeats` times over `applies` eager applies between two device events;

@@ -1,5 +1,6 @@
 """Per-step kernel breakdown from a rocprofv3 kernel_trace.csv (GPU dev tool): takes the interval between two
-consecutive adam_kernel dispatches (one train step) in the middle of the run and groups kernel time.
+consecutive Adam update dispatches (adam_stride_kernel / adam_blocks_kernel: one train step) in the middle of the
+run and groups kernel time.
 
     python tools/step_breakdown.py KERNEL_TRACE_CSV [STEP_INDEX]
 """
@@ -8,7 +9,7 @@ import csv
 import sys
 
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
-adam = [i for i, r in enumerate(rows) if "adam_kernel" in r["Kernel_Name"]]
+adam = [i for i, r in enumerate(rows) if "adam_stride_kernel" in r["Kernel_Name"] or "adam_blocks_kernel" in r["Kernel_Name"]]
 k = int(sys.argv[2]) if len(sys.argv) > 2 else len(adam) // 2
 a, b = adam[k], adam[k + 1]
 step = rows[a + 1:b + 1]

@@ -541,9 +541,13 @@ __global__ __launch_bounds__(256) void vq_reset_rows_kernel(const T* z, float* R
 // One wave per code k, lane d = embedding dimension. With esq / E3 (nullable) the codebook's derived state is
 // written in the same pass: |e_k|^2 (the butterfly order of vq_sqnorm_kernel) and the bf16 hi/mid/lo planes
 // (vq_split3_kernel's arithmetic) — the two launches the next step's argmin needs, off the step's serial tail.
-__device__ __forceinline__ void vq_ema_apply_body(float* E, float* ET, float* m_t, float* N_t, const float* m_sumT,
-                                                  const float* n_sum, const float* RT, float g, float omg,
-                                                  float thresh, int64_t* counter, float* esq, bf16* E3, int D, int K) {
+// ok (nullable): the flag of a guarded step (vqa_grad_finite over m_sumT | n_sum): with ok[0] != 1 nothing is
+// written, the reset counter included.
+__global__ __launch_bounds__(256) void vq_ema_apply_kernel(float* E, float* ET, float* m_t, float* N_t,
+                                                          const float* m_sumT, const float* n_sum, const float* RT,
+                                                          float g, float omg, float thresh, int64_t* counter,
+                                                          float* esq, bf16* E3, int D, int K, const int* ok) {
+  if (ok && ok[0] != 1) return;  // uniform over the grid
   const int k = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int d = threadIdx.x & 63;
   if (blockIdx.x == 0 && threadIdx.x == 0) counter[0] += 1;
@@ -577,25 +581,8 @@ __device__ __forceinline__ void vq_ema_apply_body(float* E, float* ET, float* m_
   }
 }
 
-__global__ __launch_bounds__(256) void vq_ema_apply_kernel(float* E, float* ET, float* m_t, float* N_t,
-                                                          const float* m_sumT, const float* n_sum, const float* RT,
-                                                          float g, float omg, float thresh, int64_t* counter,
-                                                          float* esq, bf16* E3, int D, int K) {
-  vq_ema_apply_body(E, ET, m_t, N_t, m_sumT, n_sum, RT, g, omg, thresh, counter, esq, E3, D, K);
-}
-
-// the same update behind a device flag (vqa_grad_finite over m_sumT | n_sum): with ok[0] != 1 nothing is written,
-// the reset counter included
-__global__ __launch_bounds__(256) void vq_ema_apply_if_kernel(float* E, float* ET, float* m_t, float* N_t,
-                                                             const float* m_sumT, const float* n_sum, const float* RT,
-                                                             float g, float omg, float thresh, int64_t* counter,
-                                                             float* esq, bf16* E3, int D, int K, const int* ok) {
-  if (ok[0] != 1) return;  // uniform over the grid
-  vq_ema_apply_body(E, ET, m_t, N_t, m_sumT, n_sum, RT, g, omg, thresh, counter, esq, E3, D, K);
-}
-
 // metrics: [0] #(n_sum >= thr), [1] #(N_t >= thr), [2] -sum p log(p + 1e-8), p = n_sum / sum(n_sum)
-// ok (nullable): the flag of vq_ema_apply_if_kernel; with ok[0] != 1 the metrics stay as they are
+// ok (nullable): vq_ema_apply_kernel's flag; with ok[0] != 1 the metrics stay as they are
 __global__ __launch_bounds__(256) void vq_metrics_kernel(const float* n_sum, const float* N_t, float thresh, int K,
                                                         float* metrics, const int* ok) {
   __shared__ float red[4];
@@ -1097,7 +1084,7 @@ extern "C" int vqa_vq_ema_apply_derived(float* E, float* ET, float* m_t, float* 
   VQA_ARG(D > 0 && D <= 64 && K > 0, "vq_ema_apply: supports D <= 64 (got D=%d)", D);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(vq_ema_apply_kernel, dim3((K + 3) / 4), dim3(256), 0, s, E, ET, m_t, N_t, m_sumT, n_sum, RT, gamma,
-                     one_minus_gamma, thresh, counter, e_sqnorm, (bf16*)E3, D, K);
+                     one_minus_gamma, thresh, counter, e_sqnorm, (bf16*)E3, D, K, (const int*)nullptr);
   VQA_LAUNCHED("vq_ema_apply_kernel");
   if (metrics) {
     hipLaunchKernelGGL(vq_metrics_kernel, dim3(1), dim3(256), 0, s, n_sum, (const float*)N_t, thresh, K, metrics,
@@ -1115,9 +1102,9 @@ extern "C" int vqa_vq_ema_apply_guarded(float* E, float* ET, float* m_t, float* 
   VQA_ARG(E && ET && m_t && N_t && m_sumT && n_sum && RT && counter, "vq_ema_apply_guarded: null pointer");
   VQA_ARG(D > 0 && D <= 64 && K > 0, "vq_ema_apply_guarded: supports D <= 64 (got D=%d)", D);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(vq_ema_apply_if_kernel, dim3((K + 3) / 4), dim3(256), 0, s, E, ET, m_t, N_t, m_sumT, n_sum, RT,
-                     gamma, one_minus_gamma, thresh, counter, e_sqnorm, (bf16*)E3, D, K, ok);
-  VQA_LAUNCHED("vq_ema_apply_if_kernel");
+  hipLaunchKernelGGL(vq_ema_apply_kernel, dim3((K + 3) / 4), dim3(256), 0, s, E, ET, m_t, N_t, m_sumT, n_sum, RT, gamma,
+                     one_minus_gamma, thresh, counter, e_sqnorm, (bf16*)E3, D, K, ok);
+  VQA_LAUNCHED("vq_ema_apply_kernel");
   if (metrics) {
     hipLaunchKernelGGL(vq_metrics_kernel, dim3(1), dim3(256), 0, s, n_sum, (const float*)N_t, thresh, K, metrics, ok);
     VQA_LAUNCHED("vq_metrics_kernel");

@@ -183,61 +183,39 @@ class Adam:
     def apply(self, store, grad_scale: float = 1.0):
         if self.m is None:
             self.build(store)
-        if self.skip_nonfinite:
-            return self._apply_guarded(store, grad_scale)
+        g = store.grad[:store.size]
+        if self.skip_nonfinite:  # the flag from the aggregated gradient; the update and the increment run behind it
+            V.grad_finite(g, self.step_ok)
         lr = 0.0
         if self.scheduled:
             kind, p = self.learning_rate.device_spec()
             V.lr_schedule(self.iterations, self._lr_dev, kind, p)
         else:
             lr = self.learning_rate
-        g = store.grad[:store.size]
-        avg = (self.average, self.average_decay, self.average_start_step, self.dynamic_average_decay)
-        if not self.clip_modes:
-            if self.averaging:
-                V.adam_keras_ema(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2,
-                                 self.epsilon, grad_scale, *avg, lr_dev=self._lr_dev)
-            else:
-                V.adam_keras(store.flat, g, self.m, self.v, self.iterations, lr,
-                             self.beta_1, self.beta_2, self.epsilon, grad_scale, lr_dev=self._lr_dev)
-        else:
-            c = self._clip
-            thr = (self.clipvalue or 0.0, self.clipnorm or 0.0, self.global_clipnorm or 0.0)
-            V.grad_norm(g, c["seg_start"], c["block_seg"], grad_scale, self.clip_modes, *thr, c["seg_norm"],
-                        c["stats"], c["ws"])
-            if self.averaging:
-                V.adam_keras_clipped_ema(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2,
-                                         self.epsilon, grad_scale, c["seg_start"], c["block_seg"], self.clip_modes,
-                                         *thr, c["seg_norm"], c["stats"], *avg, lr_dev=self._lr_dev)
-            else:
-                V.adam_keras_clipped(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2,
-                                     self.epsilon, grad_scale, c["seg_start"], c["block_seg"], self.clip_modes, *thr,
-                                     c["seg_norm"], c["stats"], lr_dev=self._lr_dev)
-        V.counter_add(self.iterations, 1)
-
-    def _apply_guarded(self, store, grad_scale):
-        """apply() with skip_nonfinite: the flag from the aggregated gradient, then the same schedule, norm pass and
-        update behind it."""
-        g = store.grad[:store.size]
-        V.grad_finite(g, self.step_ok)
-        lr = 0.0
-        if self.scheduled:
-            kind, p = self.learning_rate.device_spec()
-            V.lr_schedule(self.iterations, self._lr_dev, kind, p)
-        else:
-            lr = self.learning_rate
-        clip = None
+        clip = ema = None
         if self.clip_modes:
             c = self._clip
             thr = (self.clipvalue or 0.0, self.clipnorm or 0.0, self.global_clipnorm or 0.0)
             V.grad_norm(g, c["seg_start"], c["block_seg"], grad_scale, self.clip_modes, *thr, c["seg_norm"],
                         c["stats"], c["ws"])
             clip = (c["seg_start"], c["block_seg"], self.clip_modes, *thr, c["seg_norm"], c["stats"])
-        ema = ((self.average, self.average_decay, self.average_start_step, self.dynamic_average_decay)
-               if self.averaging else None)
-        V.adam_keras_guarded(store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2, self.epsilon,
-                             grad_scale, self.step_ok, self.skipped, clip=clip, ema=ema, lr_dev=self._lr_dev)
-        V.counter_add_if(self.iterations, self.step_ok)
+        if self.averaging:
+            ema = (self.average, self.average_decay, self.average_start_step, self.dynamic_average_decay)
+        adam = (store.flat, g, self.m, self.v, self.iterations, lr, self.beta_1, self.beta_2, self.epsilon, grad_scale)
+        if self.skip_nonfinite:
+            V.adam_keras_guarded(*adam, self.step_ok, self.skipped, clip=clip, ema=ema, lr_dev=self._lr_dev)
+        elif clip and ema:
+            V.adam_keras_clipped_ema(*adam, *clip, *ema, lr_dev=self._lr_dev)
+        elif clip:
+            V.adam_keras_clipped(*adam, *clip, lr_dev=self._lr_dev)
+        elif ema:
+            V.adam_keras_ema(*adam, *ema, lr_dev=self._lr_dev)
+        else:
+            V.adam_keras(*adam, lr_dev=self._lr_dev)
+        if self.skip_nonfinite:  # `iterations` advances only when the step was applied
+            V.counter_add_if(self.iterations, self.step_ok)
+        else:
+            V.counter_add(self.iterations, 1)
 
     def _averaged(self, what, store):
         if not self.averaging:
